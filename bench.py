@@ -9,7 +9,11 @@ observations already resident in HBM.
 
 Default workload (N=1): configs[2] of BASELINE.json — the 48->512^3->12 ELU
 MLP (deterministic synthetic weights, go2_onnx_controller_amd/synth.py) at
-batch 4096 robots per GPU, fp32. Beside it, on rank 0 at N=1:
+batch 4096 robots per GPU, fp32. A plain run sets up, settles the clocks, warms
+up, times `--steps` steps and prints the result line; `--dump-outputs DIR` also
+writes the actions of the last timed step (inputs are seeded: the same
+arguments give the same inputs in every run). With `--full`, beside it, the
+host enqueue cost per launch and, on rank 0 at N=1:
   * configs[1] (batch 1): `latency_b1_p50_us` (host obs -> host action, PCIe
     included, the ONNXActor::act() contract), resident kernel and launch per call;
   * configs[4]: `gru256` — the GRU-256 policy at 4096 robots, the 100-tick
@@ -36,6 +40,7 @@ import platform
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -84,6 +89,28 @@ def host_threads():
     return (env or allowed), allowed
 
 
+def work_dir():
+    """Where this run may write what it generates (the synthetic models, the C++
+    latency driver): build/ in the tree, or, when the checkout is not writable by
+    the user who runs the benchmark, a directory of that user's under the temp dir."""
+    d = os.path.join(ROOT, "build")
+    try:
+        os.makedirs(os.path.join(d, "models"), exist_ok=True)
+        if os.access(d, os.W_OK) and os.access(os.path.join(d, "models"), os.W_OK):
+            return d
+    except OSError:
+        pass
+    d = os.path.join(tempfile.gettempdir(), f"go2pi_bench_{os.getuid()}")
+    os.makedirs(os.path.join(d, "models"), mode=0o700, exist_ok=True)
+    return d
+
+
+def synth_model(name):
+    """Path of synthetic model `name` (written if absent or stale) under work_dir()."""
+    from go2_onnx_controller_amd import synth
+    return synth.ensure_model(name, os.path.join(work_dir(), "models"))
+
+
 def _pct(ts, q):
     ts = sorted(ts)
     return ts[min(len(ts) - 1, int(len(ts) * q))]
@@ -97,7 +124,6 @@ def cpu_baseline(model_path, in_dim, batch, seconds=8.0):
     98->128^3->12 model and the synthetic 48->512^3->12 one."""
     import numpy as np
     from oracle import mlp_ref
-    from go2_onnx_controller_amd import synth
     nthr, allowed = host_threads()
     ref = mlp_ref.MlpRef.from_onnx(model_path)
     x = np.random.default_rng(1).standard_normal((batch, in_dim)).astype(np.float32)
@@ -115,7 +141,7 @@ def cpu_baseline(model_path, in_dim, batch, seconds=8.0):
     vn, nn, en = rate(nthr)
     b1 = {}
     shipped = os.path.join(ROOT, "tests", "golden", "model.onnx")
-    for key, path in (("shipped", shipped), ("mlp512", synth.ensure_model("go2_mlp_512"))):
+    for key, path in (("shipped", shipped), ("mlp512", synth_model("go2_mlp_512"))):
         r = mlp_ref.MlpRef.from_onnx(path)
         row = np.random.default_rng(2).standard_normal(r.in_dim).astype(np.float32)
         ts = r.time_b1(row, warm=1000, iters=10000)
@@ -161,9 +187,9 @@ def latency_b1_cpp(model_path, in_dim, out_dim, iters=10000, warm=1000):
     default): tests/cpp/controller_shape.cpp's `lat` mode, built here with g++ if
     absent. None when it cannot be built or run."""
     lib = os.path.join(ROOT, "go2_onnx_controller_amd", "lib")
-    exe = os.path.join(ROOT, "build", "controller_shape")
     src = os.path.join(ROOT, "tests", "cpp", "controller_shape.cpp")
     try:
+        exe = os.path.join(work_dir(), "controller_shape")
         if not os.path.exists(exe) or os.path.getmtime(exe) < os.path.getmtime(src):
             os.makedirs(os.path.dirname(exe), exist_ok=True)
             subprocess.run(["g++", "-std=c++20", "-O2", "-I" + os.path.join(ROOT, "include"), src, "-L" + lib,
@@ -198,11 +224,11 @@ def gru_leg(device, launches=20, seq_ticks=100):
     hidden rows carried in LDS between ticks (HBM only at sequence start / end);
     `per_tick`: one go2pi_run_device per tick, the hidden rows round-trip HBM."""
     import torch
-    from go2_onnx_controller_amd import Engine, synth
+    from go2_onnx_controller_amd import Engine
     dev = torch.device(f"cuda:{device}")
     B = 4096
     out = {}
-    with Engine(synth.ensure_model("go2_gru_256"), device=device, max_batch=B) as e:
+    with Engine(synth_model("go2_gru_256"), device=device, max_batch=B) as e:
         g = torch.Generator().manual_seed(5)
         obs = torch.randn((seq_ticks, B, e.in_dim), generator=g).to(dev)
         act = torch.empty((seq_ticks, B, e.out_dim), device=dev)
@@ -336,6 +362,28 @@ def load_pmc(workload, kernel):
     return None, "no committed rocprofv3 --pmc summary of this kernel"
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, name, act):
+    """Write the timed path's result of its last step (`act`, the device tensor
+    [ticks, robots, out_dim] the launches filled) as float32 to directory/name.npy
+    and describe the file. An output above DUMP_LIMIT_BYTES is cut to a fixed
+    (seed 0) sorted sample of its robot rows, the same rows in every run."""
+    import numpy as np
+    a = act.detach().cpu().numpy().astype(np.float32, copy=False)
+    info = {"file": name + ".npy", "shape_full": list(a.shape), "sampled_rows": None}
+    row_bytes = a.shape[0] * a.shape[2] * 4
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[1], size=keep, replace=False))
+        a = np.ascontiguousarray(a[:, rows, :])
+        info["sampled_rows"] = int(keep)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), a)
+    info["shape"] = list(a.shape)
+    return info
+
 
 def _free_port():
     with socket.socket() as s:
@@ -379,10 +427,16 @@ def main():
     ap.add_argument("--workload", default="go2_mlp_512_b4096", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override robots per GPU")
     ap.add_argument("--waves", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency leg")
-    ap.add_argument("--no-ctl", action="store_true", help="skip the controller-tick leg")
-    ap.add_argument("--no-gru", action="store_true", help="skip the configs[4] GRU leg")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the host enqueue cost and, on rank 0 at N=1, the batch-1 "
+                         "latency, GRU, controller-tick and cpu_baseline legs (each can be dropped with --no-*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the actions of the last timed step to DIR/actions.npy "
+                         "(float32; DIR/actions_rank<r>.npy per rank at N>1)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the batch-1 latency leg")
+    ap.add_argument("--no-ctl", action="store_true", help="with --full: skip the controller-tick leg")
+    ap.add_argument("--no-gru", action="store_true", help="with --full: skip the configs[4] GRU leg")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="process group for the barrier / max-time reduce (nccl = RCCL)")
@@ -425,11 +479,11 @@ def main():
     else:
         if local >= torch.cuda.device_count():
             sys.exit(f"rank {rank}: LOCAL_RANK {local} but only {torch.cuda.device_count()} GPU(s) visible")
-        from go2_onnx_controller_amd import Engine, synth
+        from go2_onnx_controller_amd import Engine
         torch.cuda.set_device(local)
         dev = torch.device(f"cuda:{local}")
         model_path = os.path.join(ROOT, "tests", "golden", "model.onnx") if mname == "__shipped__" \
-            else synth.ensure_model(mname)
+            else synth_model(mname)
         eng = Engine(model_path, device=local, max_batch=batch, waves=args.waves)
         in_dim, out_dim = eng.in_dim, eng.out_dim
         gen = torch.Generator(device="cpu").manual_seed(1 + rank)
@@ -455,12 +509,19 @@ def main():
         launch()
     if dev is not None:
         torch.cuda.synchronize(dev)
-        # host enqueue cost per launch (must stay below the kernel time for the GPU to stay fed)
-        h0 = time.perf_counter()
-        for _ in range(args.steps):
-            launch()
-        host_us = (time.perf_counter() - h0) / args.steps * 1e6
-        torch.cuda.synchronize(dev)
+        host_us = None
+        if args.full:
+            # host enqueue cost per launch (must stay below the kernel time for the GPU to stay fed)
+            h0 = time.perf_counter()
+            for _ in range(args.steps):
+                launch()
+            host_us = (time.perf_counter() - h0) / args.steps * 1e6
+            torch.cuda.synchronize(dev)
+        if args.dump_outputs and eng.cost["has_gru"]:
+            # a recurrent policy's last step depends on every step before it, and the settle
+            # phase runs for a time, not a count: start the timed steps from h = 0
+            eng.reset_hidden()
+            torch.cuda.synchronize(dev)
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
     # ---- the timed region: barrier + sync on both sides, max over ranks
@@ -518,12 +579,14 @@ def main():
         achieved_tf = flops_launch / (kernel_ms * 1e-3) / 1e12
         kernel_name = eng.batched_kernel
         traffic, traffic_note = load_pmc(args.workload, kernel_name)
+        if args.dump_outputs:
+            out["outputs"] = dump_outputs(args.dump_outputs, "actions" if world == 1 else f"actions_rank{rank}", act)
         eng.close()
         out.update({
             "kernel": kernel_name,
             "kernel_us": round(kernel_ms * 1e3, 3),
             "kernel_us_min_max_over_ranks": [round(k_min * 1e3, 3), round(k_max * 1e3, 3)],
-            "host_enqueue_us": round(host_us, 3),
+            "host_enqueue_us": round(host_us, 3) if host_us is not None else None,
             "roofline": {"bound": "mfma", "achieved": round(achieved_tf, 3), "peak": PEAK_FP32_TFLOPS,
                          "unit": "TFLOP/s", "frac": round(achieved_tf / PEAK_FP32_TFLOPS, 4),
                          "frac_per_gpu_min": round(flops_launch / (k_max * 1e-3) / 1e12 / PEAK_FP32_TFLOPS, 4),
@@ -537,7 +600,7 @@ def main():
             out["hidden_residency"] = "lds"
         elif cost["has_gru"]:
             out["hidden_residency"] = "hbm"
-    if rank == 0 and world == 1 and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.dry_run:
         if not args.no_latency:
             # the ONNXActor shim's default (resident kernel, 100 ms idle bound), then one launch per call
             p50, p99 = latency_b1(model_path, local, resident_ms=100)
@@ -569,8 +632,7 @@ def main():
                 out["latency_b1_act_cpp"] = cpp
             # the recurrent policy (configs[4]'s GRU-256) at batch 1: the resident kernel's GRU
             # form (hidden rows carried inside the live kernel), then one fused launch per call
-            from go2_onnx_controller_amd import synth as _synth
-            gru_path = _synth.ensure_model("go2_gru_256")
+            gru_path = synth_model("go2_gru_256")
             p50, p99 = latency_b1(gru_path, local, resident_ms=100)
             out["latency_b1_gru_p50_us"] = round(p50, 2)
             out["latency_b1_gru_p99_us"] = round(p99, 2)
@@ -579,7 +641,7 @@ def main():
             out["latency_b1_gru_launch_p99_us"] = round(p99, 2)
             # LSTM-256 (the same head): resident (h as granules, c in the owning
             # workgroups' LDS), then one fused launch per call
-            lstm_path = _synth.ensure_model("go2_lstm_256")
+            lstm_path = synth_model("go2_lstm_256")
             p50, p99 = latency_b1(lstm_path, local, resident_ms=100)
             out["latency_b1_lstm_p50_us"] = round(p50, 2)
             out["latency_b1_lstm_p99_us"] = round(p99, 2)

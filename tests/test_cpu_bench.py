@@ -49,6 +49,67 @@ def test_bench_failing_rank_fails_the_job():
     assert r.returncode != 0
 
 
+def test_bench_options_parse_and_line_fields():
+    """--full and --dump-outputs exist; a dry run (no device work) computes nothing, so it
+    writes no outputs, and its line carries the headline fields with ms_per_step."""
+    r = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dry-run", "--full", "--dump-outputs",
+              os.path.join(ROOT, "build", "never_written")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1
+    assert d["unit"] == "control steps/sec" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] >= 0 and d["value"] > 0
+    assert not os.path.exists(os.path.join(ROOT, "build", "never_written"))
+
+
+def test_models_go_elsewhere_when_the_tree_cannot_be_written(tmp_path, monkeypatch):
+    """The benchmark may run from a checkout its user cannot write: what it generates goes
+    to build/ in the tree when that can be made, else to a per-user directory under the
+    temp dir, and the model written there is the pinned one."""
+    import hashlib
+    import tempfile
+    sys.path.insert(0, ROOT)
+    import bench
+    from go2_onnx_controller_amd import synth
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    assert bench.work_dir() == str(tmp_path / "build")
+    blocker = tmp_path / "not_a_directory"
+    blocker.write_text("")
+    monkeypatch.setattr(bench, "ROOT", str(blocker))  # build/ cannot be made under a file
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path / "tmp"))
+    (tmp_path / "tmp").mkdir()
+    d = bench.work_dir()
+    assert d.startswith(str(tmp_path / "tmp")) and os.path.isdir(os.path.join(d, "models"))
+    path = bench.synth_model("tiny")
+    assert os.path.dirname(path) == os.path.join(d, "models")
+    assert hashlib.sha256(open(path, "rb").read()).hexdigest() == synth.sha256("tiny")
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """dump_outputs writes float32 [ticks, robots, out]; above the size limit it keeps a
+    fixed sorted sample of the robot rows, the same rows on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    act = torch.arange(3 * 50 * 12, dtype=torch.float32).reshape(3, 50, 12)
+    info = bench.dump_outputs(str(tmp_path / "a"), "actions", act)
+    a = np.load(tmp_path / "a" / "actions.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, act.numpy())
+    assert info["file"] == "actions.npy" and info["sampled_rows"] is None and info["shape"] == [3, 50, 12]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 7 * 3 * 12 * 4 + 5)  # room for 7 robots' rows
+    got = []
+    for sub in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / sub), "actions", act)
+        got.append(np.load(tmp_path / sub / "actions.npy"))
+        assert info["sampled_rows"] == 7 and info["shape"] == [3, 7, 12] and info["shape_full"] == [3, 50, 12]
+        assert got[-1].nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(got[0], got[1])
+    rows = (got[0][0, :, 0] / 12).astype(int)  # element [0, r, 0] of `act` is 12 r
+    assert len(set(rows)) == 7 and list(rows) == sorted(rows)
+    assert np.array_equal(got[0], act.numpy()[:, rows, :])
+
+
 def test_traffic_null_when_profile_is_stale(tmp_path, monkeypatch):
     """roofline.traffic comes from the committed --pmc summary only while the kernel
     sources are the ones it was measured on: a summary entry

@@ -47,7 +47,7 @@ def main():
         for name, path, env in vs:
             e = dict(os.environ, GO2PI_LIB=path, **env)
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", args.workload, "--steps",
-                   str(args.steps), "--no-cpu", "--no-latency", "--no-gru"] + ([] if args.ctl else ["--no-ctl"])
+                   str(args.steps), "--no-cpu", "--no-latency", "--no-gru"] + (["--full"] if args.ctl else ["--no-ctl"])
             p = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=300)
             if p.returncode:
                 print(f"{name}: bench failed\n{p.stderr[-2000:]}", flush=True)

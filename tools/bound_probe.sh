@@ -12,7 +12,7 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 600 python3 -u -m pytest tests/ -m gpu -x -q --timeout 120 --timeout-method thread > $O/tests.log 2>&1 || { echo "gpu tests failed"; tail -30 $O/tests.log; exit 1; }
   tail -2 $O/tests.log
 fi
-timeout -k 10 300 python3 $R/bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json
 export GO2PI_DIAG_STAMPS=1
 for v in ${VARIANTS:-clock noload_clock nomfma_clock}; do

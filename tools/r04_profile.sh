@@ -6,10 +6,11 @@
 # tools/summarize_prof.py --round r04.
 set -o pipefail
 mkdir -p gpurun_out
+O=$_  # the results directory made above
 TAG=mlp512 STEPS=300 ARGS="--no-cpu --no-latency --no-ctl --no-gru" bash tools/profile.sh || exit 1
 TAG=gru256 STEPS=100 ARGS="--no-cpu --no-latency --no-ctl --no-gru --workload go2_gru_256_b4096" bash tools/profile.sh || exit 1
 TAG=gru256seq STEPS=40 ARGS="--no-cpu --no-latency --no-ctl --no-gru --workload go2_gru_256_b4096_seq100" bash tools/profile.sh || exit 1
-TAG=ctl STEPS=50 ARGS="--no-cpu --no-gru" bash tools/profile.sh || exit 1
+TAG=ctl STEPS=50 ARGS="--full --no-cpu --no-gru" bash tools/profile.sh || exit 1
 # keep what tools/summarize_prof.py reads (the per-dispatch traces would push gpurun_out
 # past what the box copies back)
 find gpurun_out -path '*prof_*' -type f ! -name 'run_kernel_stats.csv' ! -name 'run_counter_collection.csv' ! -name '*.log' -delete
@@ -22,5 +23,5 @@ if [ -f go2_onnx_controller_amd/lib/diag/libgo2pi_clock.so ]; then
   unset GO2PI_LIB GO2PI_DIAG_STAMPS
   echo clocks done
 fi
-timeout -k 10 400 python bench.py > gpurun_out/bench_full.json 2> gpurun_out/bench_full.err || exit 1
+timeout -k 10 400 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err || exit 1
 cat gpurun_out/bench_full.json

@@ -5,6 +5,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/gpurun_out/q
+O=$_  # the results directory made above
 bash $R/tools/gpu_tests.sh || exit 1
 bash $R/tools/r04_latency.sh || exit 1
 if [ -f $R/go2_onnx_controller_amd/lib/diag/libgo2pi_clock.so ]; then
@@ -15,5 +16,5 @@ if [ -f $R/go2_onnx_controller_amd/lib/diag/libgo2pi_clock.so ]; then
   unset GO2PI_LIB GO2PI_DIAG_STAMPS
   echo clocks done
 fi
-timeout -k 10 400 python3 $R/bench.py > $R/gpurun_out/q/bench.json 2> $R/gpurun_out/q/bench.err || { echo "bench failed"; tail -20 $R/gpurun_out/q/bench.err; exit 1; }
+timeout -k 10 400 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 cat $R/gpurun_out/q/bench.json

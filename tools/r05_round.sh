@@ -13,7 +13,7 @@ timeout -k 10 1000 python3 -u -m pytest $R/tests -m gpu -x -q --timeout 120 --ti
 tail -2 $O/tests.log
 [ -n "$NO_LAT" ] || bash $R/tools/r05_latency.sh > $O/lat.log 2>&1 || { echo "latency failed"; tail -20 $O/lat.log; exit 1; }
 grep -E "round|p50" $O/lat/ab.txt | tail -18
-timeout -k 10 600 python3 $R/bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json
 if [ -x $R/tools/launch_gap.bin ]; then
   timeout -k 10 120 $R/tools/launch_gap.bin > $O/launch_gap.txt 2>&1 || { echo "launch_gap failed"; cat $O/launch_gap.txt; exit 1; }

@@ -15,7 +15,7 @@ echo clocks done
 [ -x tools/launch_probe.bin ] && { timeout -k 10 120 tools/launch_probe.bin > $O/launch_probe.txt 2>&1 || exit 1; }
 M512=$(python3 -c "from go2_onnx_controller_amd import synth; print(synth.ensure_model('go2_mlp_512'))")
 [ -x tools/batched_probe.bin ] && { timeout -k 10 120 tools/batched_probe.bin $M512 4096 1000 > $O/batched_probe.txt 2>&1 || exit 1; }
-timeout -k 10 500 python3 bench.py > $O/bench_full.json 2> $O/bench_full.err || { tail -20 $O/bench_full.err; exit 1; }
+timeout -k 10 500 python3 bench.py --full > $O/bench_full.json 2> $O/bench_full.err || { tail -20 $O/bench_full.err; exit 1; }
 cat $O/bench_full.json
 for w in go2_gru_256_b4096 go2_lstm_256_b4096 go2_lstm_256_b4096_seq100; do
   timeout -k 10 300 python3 bench.py --workload $w --no-cpu --no-latency --no-ctl --no-gru > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }

@@ -11,6 +11,6 @@ TAG=mlp512 STEPS=300 ARGS="--no-cpu --no-latency --no-ctl --no-gru" bash tools/p
 TAG=gru256 STEPS=100 ARGS="--no-cpu --no-latency --no-ctl --no-gru --workload go2_gru_256_b4096" bash tools/profile.sh || exit 1
 TAG=gru256seq STEPS=40 ARGS="--no-cpu --no-latency --no-ctl --no-gru --workload go2_gru_256_b4096_seq100" bash tools/profile.sh || exit 1
 TAG=lstm256 STEPS=100 ARGS="--no-cpu --no-latency --no-ctl --no-gru --workload go2_lstm_256_b4096" bash tools/profile.sh || exit 1
-TAG=ctl STEPS=50 ARGS="--no-cpu --no-gru" bash tools/profile.sh || exit 1
+TAG=ctl STEPS=50 ARGS="--full --no-cpu --no-gru" bash tools/profile.sh || exit 1
 find gpurun_out -path '*prof_*' -type f ! -name 'run_kernel_stats.csv' ! -name 'run_counter_collection.csv' ! -name '*.log' -delete
 echo profiles done
