@@ -109,6 +109,121 @@ __device__ __forceinline__ void with_act(int act, F &&f) {
   }
 }
 
+// Sum over the 64 lanes of a wave, the same value in every lane, on DPP moves (no LDS
+// crossbar round trips: six dependent __shfl_xor steps were most of the LN pass's
+// time). Within each row of 16 lanes: quad_perm [1,0,3,2] and [2,3,0,1], then row_ror:4
+// and row_ror:8; lanes 0, 16, 32 and 48 then hold their row's sum, read as scalars and
+// added in that order. The order of the additions depends on the lane numbers alone.
+template <int CTRL>
+__device__ __forceinline__ float dpp_move(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+  v += dpp_move<0xb1>(v);   // quad_perm:[1,0,3,2]
+  v += dpp_move<0x4e>(v);   // quad_perm:[2,3,0,1]
+  v += dpp_move<0x124>(v);  // row_ror:4
+  v += dpp_move<0x128>(v);  // row_ror:8
+  const int i = __builtin_bit_cast(int, v);
+  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 0));
+  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 16));
+  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 32));
+  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 48));
+  return ((r0 + r1) + r2) + r3;
+}
+
+// A layer's LayerNormalization parameters (DevLayer), read once and passed by value.
+struct LnP {
+  const float *g, *b;  // [N_pad], zero padded
+  int N;
+  float eps;
+  int act;             // a pre-LN layer's activation, applied after the normalisation
+  float alpha, beta;
+};
+
+__device__ __forceinline__ LnP ln_of(const DevLayer &L) {
+  return LnP{L.ln_g, L.ln_b, L.N, L.ln_eps, L.ln_act, L.ln_alpha, L.ln_beta};
+}
+
+typedef __attribute__((address_space(3))) float lds_float;
+
+// ONNX LayerNormalization (opset 17) of LDS rows, in place, one row at a time by the
+// calling wave: rows r0, r0 + rs, ... < r1 of X (LDS, stride floats apart), over columns
+// [0, N): lane j owns columns j, j + 64, ...; mean, then the variance of x - mean in a
+// second pass (biased, fp32), then (x - mean) * rstd * g + b and, for a pre-LN layer,
+// the layer's activation. Columns [N, N_pad) are excluded by index and left as they are
+// (act(0) of the dense store: finite). The order of every addition depends on the column
+// index (and N) alone, so a row's result does not depend on where it sits in a tile or
+// batch. The caller's waves are converged (all 64 lanes active); no barrier inside.
+//
+// N <= 64 * LN_U (every policy width up to 512): a lane's columns of the row live in
+// registers between the three passes (one LDS read per element), and Scale / B are
+// loaded once for all of the wave's rows, before the first row's statistics (their L2
+// latency overlaps them). Wider layers re-read the row in each pass.
+//
+// A real call, not inlined: inlined into the batched body it cost the 16-wave kernel
+// (128 VGPRs per lane) three spilled registers; as a call, the kernels around it keep
+// the registers they had.
+constexpr int LN_U = 8;
+
+inline __device__ __noinline__ void ln_rows(float *X, int stride, int r0, int r1, int rs, LnP q, int lane) {
+  lds_float *Xl = (lds_float *)X;
+  const int N = q.N;
+  const float fn = (float)N;
+  const ActP ap{q.act, q.alpha, q.beta};
+  if (N <= 64 * LN_U) {
+    float g[LN_U], b[LN_U];
+#pragma unroll
+    for (int u = 0; u < LN_U; ++u) {
+      const int k = lane + 64 * u;
+      g[u] = k < N ? q.g[k] : 0.f;
+      b[u] = k < N ? q.b[k] : 0.f;
+    }
+    for (int r = r0; r < r1; r += rs) {
+      lds_float *row = Xl + r * stride;
+      float x[LN_U];
+#pragma unroll
+      for (int u = 0; u < LN_U; ++u) x[u] = lane + 64 * u < N ? row[lane + 64 * u] : 0.f;
+      float s = 0.f;
+#pragma unroll
+      for (int u = 0; u < LN_U; ++u) s += x[u];  // (columns past N add an exact 0)
+      const float mean = wave_sum(s) / fn;
+      float v = 0.f;
+#pragma unroll
+      for (int u = 0; u < LN_U; ++u) {
+        const float d = lane + 64 * u < N ? x[u] - mean : 0.f;
+        x[u] = d;
+        v = fmaf(d, d, v);
+      }
+      const float rstd = 1.f / sqrtf(wave_sum(v) / fn + q.eps);
+      with_act(q.act, [&](auto act_k) {
+        constexpr int ACT = decltype(act_k)::value;
+#pragma unroll
+        for (int u = 0; u < LN_U; ++u)
+          if (lane + 64 * u < N) row[lane + 64 * u] = act_t<ACT>(ap, fmaf(x[u] * rstd, g[u], b[u]));
+      });
+    }
+    return;
+  }
+  for (int r = r0; r < r1; r += rs) {
+    lds_float *row = Xl + r * stride;
+    float s = 0.f;
+    for (int k = lane; k < N; k += 64) s += row[k];
+    const float mean = wave_sum(s) / fn;
+    float v = 0.f;
+    for (int k = lane; k < N; k += 64) {
+      const float d = row[k] - mean;
+      v = fmaf(d, d, v);
+    }
+    const float rstd = 1.f / sqrtf(wave_sum(v) / fn + q.eps);
+    with_act(q.act, [&](auto act_k) {
+      constexpr int ACT = decltype(act_k)::value;
+      for (int k = lane; k < N; k += 64)
+        row[k] = act_t<ACT>(ap, fmaf((row[k] - mean) * rstd, q.g[k], q.b[k]));
+    });
+  }
+}
+
 // The action epilogue (go2pi_opts and a graph's trailing Clip / scalar Mul):
 // y <- scale * clip(tanh?(y), lo, hi); the clip passes a NaN through, as ONNX Clip.
 // Post: its program fields read once, by value — a loop that stores the actions

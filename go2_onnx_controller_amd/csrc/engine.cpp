@@ -747,6 +747,14 @@ void set_ctl_params(go2pi_engine &e, const go2pi_ctl_params &cp) {
   hip_check(hipMemcpy(e.d_ctl, &d, sizeof(d), hipMemcpyHostToDevice), "hipMemcpy");
 }
 
+// A policy with a LayerNormalization on any layer: served by the general batched body
+// and the GEMV chain only (no pipeline / lean kernel, latency kernel or resident form).
+bool has_ln(const go2pi::Model &m) {
+  for (const auto &d : m.layers)
+    if (d.ln) return true;
+  return false;
+}
+
 // The 4-wave uniform-MLP pipeline (fused_impl.hpp w4_step) applies to a policy
 // whose hidden layers are all 64 * TPW wide (TPW = 2, 4 or 8) with one
 // activation, and whose final layer is at most 2 tiles wide (1 at TPW = 8); a GRU
@@ -758,6 +766,7 @@ bool w4_eligible(const go2pi_engine &e, const go2pi::Model &m) {
   if (m.has_gru && m.gru.H % 64) return false;
   if (m.has_gru && m.gru.cell == 0 && m.gru.lbr == 0) return false;  // the two-pass cell: generic body only
   if (std::getenv("GO2PI_NO_HEAD_FUSE") || std::getenv("GO2PI_NO_W4")) return false;  // env: A/B diagnostics only
+  if (has_ln(m)) return false;  // LayerNormalization: the general body only (fused_impl.hpp ln_tile)
   const int tpw = ceil64(m.layers[0].N) / 64, t_last = ceil16(m.layers[nl - 1].N) / 16;
   if (!(tpw == 2 || tpw == 4 || tpw == 8) || t_last > (tpw == 8 ? 1 : 2)) return false;
   for (int l = 0; l + 1 < nl; ++l)
@@ -840,6 +849,25 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
     L.act = m.layers[l].act;
     L.alpha = m.layers[l].alpha;
     L.beta = m.layers[l].beta;
+    if (const auto &d = m.layers[l]; d.ln) {
+      // scale and bias padded to N_pad with zeros; a pre-LN layer's dense store writes
+      // the raw pre-activation and the LN pass applies the layer's activation
+      std::vector<float> g(np, 0.f), bb(np, 0.f);
+      std::copy(d.ln_g.begin(), d.ln_g.end(), g.begin());
+      std::copy(d.ln_b.begin(), d.ln_b.end(), bb.begin());
+      L.ln = d.ln;
+      L.ln_eps = d.ln_eps;
+      L.ln_g = e.upload(g);
+      L.ln_b = e.upload(bb);
+      if (d.ln == 1) {
+        L.ln_act = L.act;
+        L.ln_alpha = L.alpha;
+        L.ln_beta = L.beta;
+        L.act = go2pi::ACT_NONE;
+        L.alpha = L.beta = 0.f;
+      }
+      wbytes += 4.0 * 2.0 * d.N;
+    }
     maxw = std::max({maxw, kp, np});
     flops += 2.0 * m.layers[l].K * m.layers[l].N;
     wbytes += 4.0 * ((double)m.layers[l].K * m.layers[l].N + m.layers[l].N);
@@ -897,7 +925,8 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   // group set per wave (T >= waves) is folded into the predecessor's epilogue
   if (p.nl >= 2 && !std::getenv("GO2PI_NO_HEAD_FUSE")) {  // env: A/B diagnostics only
     const int t_last = p.L[p.nl - 1].N_pad / 16, t_prev = p.L[p.nl - 2].N_pad / 16;
-    if (t_last <= 2 && t_prev >= e.waves) p.head_fuse = t_last;
+    // (not behind a LayerNormalization: dense_layer_head feeds the head from un-normalised registers)
+    if (t_last <= 2 && t_prev >= e.waves && !p.L[p.nl - 2].ln) p.head_fuse = t_last;
   }
   // 4-wave uniform-MLP pipeline (kernels.hip, w4_step): a fused head, and
   // every hidden layer exactly one group of 2, 4 or 8 tiles per wave. It is the
@@ -985,12 +1014,13 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
     for (int l = 0; l < p.nl; ++l) kmax = std::max(kmax, p.L[l].K_pad);
     const bool lat_shape = kmax <= 1024 && go2pi::latency_grid(p) <= 256 && e.small_batch > 0 &&
                            !std::getenv("GO2PI_SMALL_CHAIN");  // env: diagnostics, force the GEMV chain
-    e.latency_ok = !m.has_gru && lat_shape;
+    e.latency_ok = !m.has_gru && lat_shape && !has_ln(m);
     // the resident kernel's GRU / LSTM form (resident.hip, RNN): the cell tiled in front
     // of the dense layers, h' carried between requests as granules (an LSTM's c in the
     // owning workgroups' LDS)
     const bool res_rnn = m.has_gru && ((m.gru.cell == 0 && m.gru.lbr == 1) || m.gru.cell == 1) && m.gru.H % 64 == 0 &&
-                         p.gru.I_pad + m.gru.H <= 512 && (m.gru.H >> 4) <= 256 && lat_shape && e.opts.resident_ms > 0;
+                         p.gru.I_pad + m.gru.H <= 512 && (m.gru.H >> 4) <= 256 && lat_shape && e.opts.resident_ms > 0 &&
+                         !has_ln(m);
     e.palloc(&e.h_err, &e.m_err, 512);
     p.err = e.m_err + 64;  // batched kernel hand-off timeouts
     if (e.latency_ok || res_rnn) {

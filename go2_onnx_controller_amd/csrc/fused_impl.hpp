@@ -427,6 +427,15 @@ __device__ __forceinline__ void dense_layer(const DevProgram &P, const DevLayer 
   }
 }
 
+// LayerNormalization of a layer's 16-row output tile, in place in the LDS buffer the
+// next layer reads (after the layer's barrier; the caller follows it with one barrier):
+// rows over the NW waves, columns over the lanes (device_fn.hpp ln_rows). No LDS of its
+// own. Rows past the batch hold the bias chain's finite values and stay finite.
+template <int NW>
+__device__ __forceinline__ void ln_tile(const DevLayer &L, float *Y, int ys, int wave, int lane) {
+  ln_rows(Y, ys, wave, GO2PI_TILE_ROWS, NW, ln_of(L), lane);
+}
+
 // GRU cell (ONNX semantics, linear_before_reset = 1) for one 16-robot tile.
 // X: LDS rows [16][xs] holding x in columns [0, I_pad); Hs: LDS hidden rows
 // (stride xs). Writes h' to Y[:, 0:H]; the caller copies it back into Hs after
@@ -2086,6 +2095,12 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
       }
       dense_layer<NW>(P, P.L[l], X, Y, S, scratch, wave, lane, last, ac, cv, row0, B);
       __syncthreads();  // a workgroup barrier after every layer (dense_acc: flags measured slower)
+      if constexpr (W4T == 0) {
+        if (P.L[l].ln) {  // uniform over the workgroup: every wave reaches the barrier below
+          ln_tile<NW>(P.L[l], Y, S, wave, lane);
+          __syncthreads();
+        }
+      }
       GO2PI_STAMP(P, tid == 0 && step == 0 && l < 9, 6 + l);  // slots 6..14 (15 is the controller tick's)
       float *t = X;
       X = Y;

@@ -67,6 +67,13 @@ __global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram 
     xs[b * K_pad + k] = v;
   }
   __syncthreads();
+  // The previous layer's LayerNormalization (it stored its un-normalised output: a
+  // pre-LN layer its raw pre-activation): every workgroup holds the whole rows, so
+  // each normalises its own copy while staging, one row per wave. No extra launch.
+  if (layer > 0 && P.L[layer - 1].ln) {  // uniform over the workgroup
+    ln_rows(xs, K_pad, wave, B, GEMV_WAVES, ln_of(P.L[layer - 1]), lane);
+    __syncthreads();
+  }
   float p[GO2PI_SMALL_MAXB];
 #pragma unroll
   for (int b = 0; b < GO2PI_SMALL_MAXB; ++b) p[b] = 0.f;

@@ -667,6 +667,44 @@ Model parse_onnx(const uint8_t *data, size_t n) {
       m.layers.push_back(std::move(d));
       last_has_act = false;
       pending_bias_ok = true;
+    } else if (nd.op == "LayerNormalization") {
+      // opset 17, over the feature axis of the [batch, N] value: right after a layer's
+      // Gemm / bias ("pre": the activation, if any, follows it) or right after its
+      // activation ("post"). Anything else is refused, never approximated.
+      if (nd.in.size() < 2 || nd.in[0] != cur) fail("LayerNormalization: the activation must be input X");
+      if (at_input) fail("LayerNormalization before the first layer is unsupported");
+      if (m.layers.empty()) fail("LayerNormalization right after the recurrent cell is unsupported");
+      Dense &d = m.layers.back();
+      if (d.ln) fail("a second LayerNormalization on the same layer is unsupported");
+      if (post_clip) fail("LayerNormalization after a Clip that follows an activation is unsupported");
+      if (!col_scale.empty()) fail("a Mul or Div between an activation and its LayerNormalization is unsupported");
+      const int64_t axis = nd.iattr("axis", -1);
+      if (axis != -1 && axis != 1) fail("LayerNormalization: axis must be the feature axis (-1 or 1)");
+      if (nd.iattr("stash_type", 1) != 1) fail("LayerNormalization: stash_type other than 1 is unsupported");
+      for (size_t k = 1; k < nd.out.size(); ++k) {
+        if (nd.out[k].empty()) continue;
+        bool is_out = false;
+        for (auto &o : m.outputs) is_out |= o.name == nd.out[k];
+        if (is_out || consumers.count(nd.out[k]))
+          fail("LayerNormalization: the Mean / InvStdDev outputs must not be consumed");
+      }
+      auto param = [&](const std::string &name, const char *what) {
+        auto pi = inits.find(name);
+        if (pi == inits.end()) fail(std::string("LayerNormalization: ") + what + " must be a constant");
+        if (pi->second.dtype != 1) fail(std::string("LayerNormalization: ") + what + " must be a FLOAT tensor");
+        if (pi->second.numel() != d.N || (int64_t)pi->second.f.size() != d.N)
+          fail(std::string("LayerNormalization: ") + what + " must have the layer's " + std::to_string(d.N) + " elements");
+        return pi->second.f;
+      };
+      d.ln_g = param(nd.in[1], "Scale");
+      if (nd.in.size() > 2 && !nd.in[2].empty()) d.ln_b = param(nd.in[2], "B");
+      else d.ln_b.assign(d.N, 0.f);
+      d.ln_eps = nd.fattr("epsilon", 1e-5f);
+      d.ln = last_has_act ? 2 : 1;
+      pending_bias_ok = false;
+    } else if (!m.layers.empty() && m.layers.back().ln == 1 && !last_has_act &&
+               (nd.op == "Add" || nd.op == "Mul" || nd.op == "Div" || nd.op == "Sub")) {
+      fail(nd.op + " between a LayerNormalization and its activation is unsupported");
     } else if (nd.op == "Add" && is_init(other_input())) {
       const Tensor &C = init(other_input());
       if (m.layers.empty() || last_has_act || !pending_bias_ok) fail("Add: only a bias right after Gemm/MatMul is supported");
@@ -810,6 +848,7 @@ Model parse_onnx(const uint8_t *data, size_t n) {
   }
 
   if (m.layers.empty()) fail("policy has no linear layer");
+  if (m.layers.back().ln) fail("LayerNormalization on the output layer is unsupported");
   if (rnn_node != SIZE_MAX) {
     // The recurrent state I/O listed as (h, c) after the observation / action, whatever
     // the graph's order: traced by name to the cell's initial_h / initial_c (inputs 5,
@@ -952,7 +991,9 @@ std::string inspect_json(const Model &m) {
     const auto &d = m.layers[l];
     j += (l ? "," : "") + std::string("{\"K\":") + std::to_string(d.K) + ",\"N\":" + std::to_string(d.N) +
          ",\"act\":" + std::to_string(d.act) + ",\"alpha\":" + json_num(d.alpha) + ",\"beta\":" + json_num(d.beta) +
-         ",\"w_sum\":" + json_num(sum_of(d.W)) + ",\"b_sum\":" + json_num(sum_of(d.b)) + "}";
+         ",\"w_sum\":" + json_num(sum_of(d.W)) + ",\"b_sum\":" + json_num(sum_of(d.b)) +
+         ",\"ln\":" + std::to_string(d.ln) + ",\"ln_eps\":" + json_num(d.ln_eps) +
+         ",\"ln_g_sum\":" + json_num(sum_of(d.ln_g)) + ",\"ln_b_sum\":" + json_num(sum_of(d.ln_b)) + "}";
   }
   j += "],\"gru\":";
   if (m.has_gru)

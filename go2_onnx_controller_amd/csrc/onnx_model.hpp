@@ -1,7 +1,7 @@
 // ONNX policy loader: a minimal protobuf reader plus a pattern matcher that
 // lowers an exported policy graph to the engine's program (dense layers with a
-// fused activation, optional leading GRU, optional affine prologue and clip
-// epilogue). Replaces what the reference gets from onnxruntime's session
+// fused activation and an optional LayerNormalization, optional leading GRU,
+// optional affine prologue and clip epilogue). Replaces what the reference gets from onnxruntime's session
 // creation (onnx_inference/src/cpp/onnx_actor.cpp:16, :23-28).
 #pragma once
 
@@ -28,6 +28,11 @@ struct Dense {
   std::vector<float> b;  // [N]
   int act = ACT_NONE;
   float alpha = 0.f, beta = 0.f;
+  // ONNX LayerNormalization (opset 17) over the layer's N features: 0 none, 1 "pre"
+  // (after the Gemm / bias, in front of the activation), 2 "post" (after the activation)
+  int ln = 0;
+  float ln_eps = 1e-5f;
+  std::vector<float> ln_g, ln_b;  // Scale, B: [N] each (B zeros when the node has none)
 };
 
 // ONNX GRU (opset 14), forward, layout 0, one layer; gates ordered z, r, h.

@@ -87,7 +87,15 @@ struct DevLayer {
   int K_pad, N_pad, N;
   int act;
   float alpha, beta;  // the activation's attributes (onnx_model.hpp Dense)
-  int pad1, pad2;
+  // LayerNormalization of this layer's output over its N features (device_fn.hpp ln_rows):
+  // 0 none, 1 pre (act above is ACT_NONE: the dense store writes the raw pre-activation
+  // and the LN pass applies ln_act), 2 post (the dense store applies act, ln_act is 0)
+  int ln;
+  float ln_eps;
+  const float *ln_g, *ln_b;  // [N_pad] each, zero padded
+  int ln_act;
+  float ln_alpha, ln_beta;
+  int pad1;
 };
 
 // The recurrent cell in front of the dense head (ONNX GRU or LSTM; the field

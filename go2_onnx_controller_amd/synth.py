@@ -62,23 +62,82 @@ def mlp_layers(dims, seed=0, first_tid=0):
     return layers
 
 
-def mlp_model_bytes(dims=(48, 512, 512, 512, 12), seed=0, act="Elu", batch="batch") -> bytes:
-    layers = mlp_layers(dims, seed)
-    nodes, inits = [], []
-    cur = "observation"
+def _per_layer(v, n):
+    """One value per hidden layer: a scalar is repeated, a sequence taken as given."""
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError(f"expected {n} per-layer values, got {len(v)}")
+        return list(v)
+    return [v] * n
+
+
+def ln_params(n, seed, tid):
+    """LayerNormalization parameters of an n-wide layer: scale 1 + U(+-0.25), bias U(+-0.25)."""
+    g = (np.float32(1.0) + uniform(seed, tid, (n,), 0.25)).astype(np.float32)
+    b = uniform(seed, tid + 1, (n,), 0.25)
+    return g, b
+
+
+_LN_TID = 1000  # LayerNormalization tensors: ids 1000 + 2 * layer (dense layers count up from 0 / 200)
+
+
+def _dense_chain(cur, layers, seed, nodes, inits, wname, nname, act, layer_norm, ln_eps, ln_bias):
+    """The Gemm (+ activation, + LayerNormalization) chain every generator ends with.
+    wname(i): layer i's (weight, bias) initialiser names; nname(i, op): the node name of
+    layer i's op, whose output is that name + "_output_0". act / layer_norm / ln_eps /
+    ln_bias: one value, or one per hidden layer. With layer_norm None the graph is byte
+    for byte what it was before LayerNormalization existed."""
+    nh = len(layers) - 1
+    acts, lns = _per_layer(act, nh), _per_layer(layer_norm, nh)
+    epss, lbs = _per_layer(ln_eps, nh), _per_layer(ln_bias, nh)
     for i, (W, b) in enumerate(layers):
-        wn, bn = f"{2 * i}.weight", f"{2 * i}.bias"
+        wn, bn = wname(i)
         inits += [(wn, W), (bn, b)]
-        last = i == len(layers) - 1
-        out = "action" if last else f"/{2 * i}/Gemm_output_0"
-        nodes.append(ow.node("Gemm", [cur, wn, bn], [out], f"/{2 * i}/Gemm",
+        last = i == nh
+        name = nname(i, "Gemm")
+        out = "action" if last else name + "_output_0"
+        nodes.append(ow.node("Gemm", [cur, wn, bn], [out], name,
                              [ow.attr_float("alpha", 1.0), ow.attr_float("beta", 1.0), ow.attr_int("transB", 1)]))
         cur = out
-        if not last:
-            aout = f"/{2 * i + 1}/{act}_output_0"
-            attrs = [ow.attr_float("alpha", 1.0)] if act == "Elu" else []
-            nodes.append(ow.node(act, [cur], [aout], f"/{2 * i + 1}/{act}", attrs))
-            cur = aout
+        if last:
+            break
+        if lns[i] not in (None, "pre", "post"):
+            raise ValueError(f"layer_norm must be None, 'pre' or 'post', not {lns[i]!r}")
+
+        def norm(x):
+            g, bb = ln_params(W.shape[0], seed, _LN_TID + 2 * i)
+            name = nname(i, "LayerNormalization")
+            inits.append((f"ln.{i}.weight", g))
+            ins = [x, f"ln.{i}.weight"]
+            if lbs[i]:
+                inits.append((f"ln.{i}.bias", bb))
+                ins.append(f"ln.{i}.bias")
+            nodes.append(ow.node("LayerNormalization", ins, [name + "_output_0"], name,
+                                 [ow.attr_int("axis", -1), ow.attr_float("epsilon", float(epss[i]))]))
+            return name + "_output_0"
+
+        if lns[i] == "pre":
+            cur = norm(cur)
+        if acts[i]:
+            name = nname(i, acts[i])
+            attrs = [ow.attr_float("alpha", 1.0)] if acts[i] == "Elu" else []
+            nodes.append(ow.node(acts[i], [cur], [name + "_output_0"], name, attrs))
+            cur = name + "_output_0"
+        if lns[i] == "post":
+            cur = norm(cur)
+
+
+def mlp_model_bytes(dims=(48, 512, 512, 512, 12), seed=0, act="Elu", batch="batch", layer_norm=None,
+                    ln_eps=1e-5, ln_bias=True) -> bytes:
+    """layer_norm: None, "pre" (Gemm -> LayerNormalization -> act: SimBa-style actors) or
+    "post" (Gemm -> act -> LayerNormalization: rl_games / brax) on every hidden layer, or a
+    sequence with one of those per hidden layer; act, ln_eps and ln_bias (False: the node
+    has no B input) take one value per hidden layer the same way."""
+    layers = mlp_layers(dims, seed)
+    nodes, inits = [], []
+    _dense_chain("observation", layers, seed, nodes, inits, lambda i: (f"{2 * i}.weight", f"{2 * i}.bias"),
+                 lambda i, op: f"/{2 * i}/Gemm" if op == "Gemm" else f"/{2 * i + 1}/{op}",
+                 act, layer_norm, ln_eps, ln_bias)
     return ow.model(nodes, inits, [("observation", [batch, dims[0]])], [("action", [batch, dims[-1]])])
 
 
@@ -90,9 +149,11 @@ def gru_params(I=48, H=256, seed=0):
     return W, R, B
 
 
-def gru_model_bytes(I=48, H=256, head=(512, 512, 512, 12), seed=0, batch="batch", lbr=1) -> bytes:
+def gru_model_bytes(I=48, H=256, head=(512, 512, 512, 12), seed=0, batch="batch", lbr=1, layer_norm=None,
+                    ln_eps=1e-5) -> bytes:
     """lbr: linear_before_reset (1: torch.onnx.export's nn.GRU and Keras' default
-    reset_after=True; 0: Keras reset_after=False and the ONNX default)."""
+    reset_after=True; 0: Keras reset_after=False and the ONNX default).
+    layer_norm / ln_eps: LayerNormalization on the head's hidden layers (mlp_model_bytes)."""
     W, R, B = gru_params(I, H, seed)
     layers = mlp_layers((H,) + tuple(head), seed, first_tid=200)
     axes = np.array([0], np.int64)
@@ -103,19 +164,8 @@ def gru_model_bytes(I=48, H=256, head=(512, 512, 512, 12), seed=0, batch="batch"
                 [ow.attr_int("hidden_size", H)] + ([ow.attr_int("linear_before_reset", 1)] if lbr else [])),
         ow.node("Squeeze", ["h_out", "axes0"], ["h_t"], "/gru/Squeeze"),
     ]
-    cur = "h_t"
-    for i, (Wl, bl) in enumerate(layers):
-        wn, bn = f"head.{i}.weight", f"head.{i}.bias"
-        inits += [(wn, Wl), (bn, bl)]
-        last = i == len(layers) - 1
-        out = "action" if last else f"/head/{i}/Gemm_output_0"
-        nodes.append(ow.node("Gemm", [cur, wn, bn], [out], f"/head/{i}/Gemm",
-                             [ow.attr_float("alpha", 1.0), ow.attr_float("beta", 1.0), ow.attr_int("transB", 1)]))
-        cur = out
-        if not last:
-            aout = f"/head/{i}/Elu_output_0"
-            nodes.append(ow.node("Elu", [cur], [aout], f"/head/{i}/Elu", [ow.attr_float("alpha", 1.0)]))
-            cur = aout
+    _dense_chain("h_t", layers, seed, nodes, inits, lambda i: (f"head.{i}.weight", f"head.{i}.bias"),
+                 lambda i, op: f"/head/{i}/{op}", "Elu", layer_norm, ln_eps, True)
     return ow.model(nodes, inits,
                     [("observation", [batch, I]), ("h_in", [1, batch, H])],
                     [("action", [batch, head[-1]]), ("h_out", [1, batch, H])])
@@ -202,6 +252,18 @@ MODELS = {
     "go2_lstm_256": lambda: lstm_model_bytes(),
     "lstm_128": lambda: lstm_model_bytes(I=30, H=128, head=(256, 256, 12), seed=15),           # 2-tile LSTM stage
     "lstm_small": lambda: lstm_model_bytes(I=10, H=32, head=(64, 6), seed=16),                 # generic body
+    # LayerNormalization policies (opset 17): "pre" Gemm -> LN -> act, "post" Gemm -> act -> LN
+    "ln_pre_small": lambda: mlp_model_bytes((40, 100, 72, 12), seed=30, layer_norm="pre"),     # widths off 16 / 64
+    "ln_post_small": lambda: mlp_model_bytes((33, 48, 80, 7), seed=31, act="Relu", layer_norm="post"),  # rl_games order
+    # pre-LN + Tanh; Relu alone; Sigmoid + post-LN without B, epsilon 1e-3, width 200 padded to 256
+    "ln_mixed": lambda: mlp_model_bytes((30, 64, 40, 200, 9), seed=32, act=("Tanh", "Relu", "Sigmoid"),
+                                        layer_norm=("pre", None, "post"), ln_eps=(1e-5, 1e-5, 1e-3),
+                                        ln_bias=(True, True, False)),
+    "ln_512_pre": lambda: mlp_model_bytes(seed=33, layer_norm="pre"),                           # the workload's shape
+    "ln_ctl_post": lambda: mlp_model_bytes((98, 128, 128, 128, 12), seed=34, layer_norm="post"),  # a controller-tick policy
+    "gru_ln": lambda: gru_model_bytes(I=10, H=32, head=(64, 6), seed=35, layer_norm="pre"),
+    # wider than the 512 columns the LN pass keeps in registers (device_fn.hpp ln_rows): its other path
+    "ln_wide_pre": lambda: mlp_model_bytes((24, 600, 8), seed=36, act="Tanh", layer_norm="pre"),
 }
 
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

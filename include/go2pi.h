@@ -74,7 +74,17 @@ typedef struct go2pi_opts {
 void go2pi_default_opts(go2pi_opts *opts);
 
 /* Load an ONNX policy (Gemm/MatMul+Add with Elu/Relu/Tanh/Sigmoid/LeakyRelu, optional GRU)
-   and upload it to the device. `opts` may be NULL (defaults). */
+   and upload it to the device. `opts` may be NULL (defaults).
+   LayerNormalization (opset 17, over the feature axis, epsilon from the attribute, Scale
+   and optional B constant, only output 0 used) is accepted on any dense layer but the last,
+   once per layer: right after the layer's Gemm / MatMul (+ bias), in front of its
+   activation if it has one ("pre"), or right after its activation ("post"). Any other
+   placement (on the observation, after the recurrent cell, on the output layer, twice on
+   a layer, with a Mul / Div / Add between it and its activation), another axis or
+   stash_type, a Scale / B of another length or not constant, and a consumed Mean /
+   InvStdDev output fail with GO2PI_E_MODEL and a message of their own. Such a policy is
+   served by the general batched kernel and, at batch <= 8, by one launch per layer; the
+   lean, single-launch and resident (resident_ms) forms do not serve it yet. */
 int go2pi_create(const char *onnx_path, const go2pi_opts *opts, go2pi_engine **out);
 int go2pi_create_from_memory(const void *onnx_bytes, size_t nbytes, const go2pi_opts *opts,
                              go2pi_engine **out);
@@ -119,7 +129,7 @@ int go2pi_sync(go2pi_engine *e);
 /* Algorithmic cost per robot-step (for roofline accounting in bench.py). */
 typedef struct go2pi_cost {
   double flops_per_row;    /* 2*MAC of every contraction (+ nothing for activations) */
-  double weight_bytes;     /* fp32 parameter bytes (unpadded) */
+  double weight_bytes;     /* fp32 parameter bytes (unpadded; LayerNormalization Scale and B included) */
   double io_bytes_per_row; /* obs + action (+ 2x hidden for recurrent) bytes */
   int32_t n_layers;
   int32_t has_gru;         /* recurrent cell in front of the dense layers: 0 none, 1 GRU, 2 LSTM */
