@@ -1057,6 +1057,13 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
       e.resident_ctl_ok = !m.has_gru;  // the controller-tick form serves dense policies
     }
   }
+  // GO2PI_EPOCH0=<u32>: the engine's first granule tag instead of 1 (diagnostics and tests: a
+  // value near 2^32 puts the tag-space wrap of next_epoch / resident_serve a few calls away
+  // instead of ~1e9; 0, the empty granule's tag, is ignored)
+  if (const char *s = std::getenv("GO2PI_EPOCH0")) {
+    const unsigned long long v = std::strtoull(s, nullptr, 0);
+    if (v >= 1 && v <= 0xFFFFFFFFull) e.epoch = (unsigned)v;
+  }
   if (std::getenv("GO2PI_DIAG_STAMPS")) {  // diagnostics: per-workgroup clock stamps
     e.n_stamps = GO2PI_STAMPS_PER_WG * ((e.opts.max_batch + GO2PI_TILE_ROWS - 1) / GO2PI_TILE_ROWS);
     p.stamps = e.dalloc<unsigned long long>(e.n_stamps);
@@ -1770,9 +1777,8 @@ int go2pi_resident_kernel(const go2pi_engine *e, char *buf, size_t cap) {
       std::snprintf(buf, cap, "%s%s",
                     go2pi::resident1_ctl_granules(e->prog) ? "policy_act1_kernel" : "policy_resident1_kernel", ring);
     } else if (e->wide) {
-      const go2pi::WideShape w = go2pi::wide_shape(e->prog);
-      const bool pro = e->prog.pre_sub || e->prog.pre_div || e->prog.pre_mul || e->prog.pre_clip;
-      std::snprintf(buf, cap, "policy_wide_kernel<%d, %d, %d, %d>%s", w.nl, w.cw, w.f0, pro ? 1 : 0, ring);
+      const go2pi::WideShape w = go2pi::wide_shape(e->prog);  // (what launch_resident_wide runs)
+      std::snprintf(buf, cap, "policy_wide_kernel<%d, %d, %d, %d>%s", w.nl, w.cw, w.f0, w.pro, ring);
     } else {
       std::snprintf(buf, cap, "policy_resident_kernel%s", ring);
     }

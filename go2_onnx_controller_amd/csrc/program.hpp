@@ -290,8 +290,11 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
 // ring must be in device memory: the host writes it through the large-BAR mapping).
 // Same request / answer / leave protocol as launch_resident1 (act() form only); gran:
 // [nl - 1][gstride >= 8 H] granules, zeroed before every launch.
+// {nl, cw, f0, pro}: the template arguments of the instantiation that serves the program
+// (pro: the build that applies the observation prologue; every shape but 4 layers of 512
+// has that build only, and runs it with identity constants where the policy has none)
 struct WideShape {
-  int nl, cw, f0;
+  int nl, cw, f0, pro;
 };
 WideShape wide_shape(const DevProgram &p);  // nl = 0: does not apply
 int launch_resident_wide(const DevProgram &p, const DevProgram *p_dev, const unsigned long long *req,

@@ -488,11 +488,13 @@ __global__ __launch_bounds__(64 * (1 + CW)) void policy_wide_kernel(const DevPro
 // ---------------------------------------------------------------------------
 // host side
 
-// {NL, CW, F0} of program p when policy_wide_kernel serves it, else NL = 0: a dense
+// {NL, CW, F0, PRO} of program p when policy_wide_kernel serves it, else NL = 0: a dense
 // policy of 3 or 4 layers whose hidden layers are all H = 256 or 512 wide, a head of
-// <= 16 outputs and layer 0 of K_pad <= 64 (<= 48 for 4 layers of 512)
+// <= 16 outputs and layer 0 of K_pad <= 64 (<= 48 for 4 layers of 512). The one place
+// that decides the instantiation: launch_resident_wide runs it, go2pi_resident_kernel
+// names it.
 WideShape wide_shape(const DevProgram &p) {
-  WideShape w{0, 0, 0};
+  WideShape w{0, 0, 0, 0};
   if (p.has_gru || p.nl < 3 || p.nl > 5 || p.L[p.nl - 1].N_pad != 16) return w;
   const int H = p.L[0].N_pad;
   if (H != 256 && H != 512) return w;
@@ -502,7 +504,12 @@ WideShape wide_shape(const DevProgram &p) {
   if (p.nl == 5 || (p.nl == 4 && H == 512 && p.L[0].K_pad > 48)) return w;  // (their registers spilled)
   w.nl = p.nl;
   w.cw = H / 64;
-  w.f0 = (w.nl == 4 && w.cw == 8) ? 12 : 16;  // (the instantiations launch_resident_wide runs)
+  // the BASELINE policy's shape (48 -> 512^3 -> 12) has two instantiations of its own
+  // (F0 = 12; without a prologue, and with one); every other shape the generic one
+  // (F0 = 16, the prologue applied: identity constants where the policy has none)
+  const bool base = w.nl == 4 && w.cw == 8;
+  w.f0 = base ? 12 : 16;
+  w.pro = (!base || p.pre_sub || p.pre_div || p.pre_mul || p.pre_clip) ? 1 : 0;
   return w;
 }
 
@@ -516,18 +523,19 @@ int launch_resident_wide(const DevProgram &p, const DevProgram *p_dev, const uns
   const WideShape w = wide_shape(p);
   if (!w.nl || !yield || gstride < GO2PI_SMALL_MAXB * 64 * w.cw) return (int)hipErrorInvalidValue;
   const size_t lds = wide_lds_bytes(w);
-  const bool pro = p.pre_sub || p.pre_div || p.pre_mul || p.pre_clip;
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(4 * w.cw), dim3(64 * (1 + w.cw)), lds, reinterpret_cast<hipStream_t>(stream), p_dev,
                        req, actg, gran, gstride, err, done, idle_ticks, yield);
     return (int)hipGetLastError();
   };
-  // the BASELINE policy's shape (48 -> 512^3 -> 12, no prologue) has its own
-  // instantiation; every other shape the generic one (F0 = 16, the prologue applied)
-  if (w.nl == 4 && w.cw == 8) return pro ? go(policy_wide_kernel<4, 8, 12, true>) : go(policy_wide_kernel<4, 8, 12, false>);
-  if (w.cw == 8) return go(policy_wide_kernel<3, 8, 16, true>);
-  if (w.nl == 3) return go(policy_wide_kernel<3, 4, 16, true>);
-  return go(policy_wide_kernel<4, 4, 16, true>);
+  // exactly the instantiation wide_shape names
+  auto is = [&](int nl, int cw, int f0, int pro) { return w.nl == nl && w.cw == cw && w.f0 == f0 && w.pro == pro; };
+  if (is(4, 8, 12, 0)) return go(policy_wide_kernel<4, 8, 12, false>);
+  if (is(4, 8, 12, 1)) return go(policy_wide_kernel<4, 8, 12, true>);
+  if (is(3, 8, 16, 1)) return go(policy_wide_kernel<3, 8, 16, true>);
+  if (is(3, 4, 16, 1)) return go(policy_wide_kernel<3, 4, 16, true>);
+  if (is(4, 4, 16, 1)) return go(policy_wide_kernel<4, 4, 16, true>);
+  return (int)hipErrorInvalidValue;
 }
 
 }  // namespace go2pi

@@ -4,8 +4,10 @@ MatMul + Add, Sub/Div input normalisation, LeakyRelu / Sigmoid, trailing
 Tanh + Clip, Clip between dense layers (ReLU6), Constant nodes, Mul by a
 constant at the input / after a Gemm / after an activation / at the output,
 Selu / Softplus / HardSigmoid / HardSwish / Softsign, a Slice -> per-block
-normalisation -> Concat observation front-end. Built with the repo's own
-writer; evaluated by the oracle."""
+normalisation -> Concat observation front-end; and 256- / 512-wide policies
+with a front-end, per-layer activation parameters and an output tail
+(WIDE_VARIANTS, WIDE_EDGES). Built with the repo's own writer; evaluated by
+the oracle."""
 import numpy as np
 
 from go2_onnx_controller_amd import onnx_writer as ow
@@ -184,6 +186,171 @@ VARIANTS = ["gemm_transB0_alpha_beta", "matmul_add_sigmoid", "normalized_tanh_cl
 # row must come out as a NaN action row
 NAN_VARIANTS = ["normalized_tanh_clip", "relu6_mid_clip", "relu6_pipeline", "const_scales"]
 
+
+# ---------------------------------------------------------------------------
+# Wide policies (every hidden layer 256 or 512 wide): the shapes the resident wide-policy
+# kernel (resident_wide.hip policy_wide_kernel) serves at batch <= 8, with a real
+# observation front-end, a different activation (or different attributes) per layer and an
+# output tail that binds. Weights are synth.mlp_layers' U(+-1/sqrt(fan_in)), so activations
+# stay O(1); the head's weight and bias are multiplied by `head` so that the output reaches
+# the tail's bounds. Kept out of VARIANTS (which parametrises the older tests).
+#
+# front: observation ops in order, each ("Sub" | "Div" | "Mul", "vec" | "scalar") or
+# ("Clip", lo, hi); const_nodes: their constants as Constant nodes instead of initialisers.
+# acts: one (op, attributes) per hidden layer; ("Clip", lo, hi) is a Clip activation.
+# head_act: the head's activation; tail: ("Clip", lo, hi) / ("Mul", k) after it.
+_WIDE = {
+    # 48 -> 512^3 -> 12, the BASELINE policy's shape with a prologue: policy_wide_kernel<4, 8, 12, 1>
+    # (one activation on every hidden layer, as the 4-wave pipeline needs: only then is the
+    # 48-wide observation padded to 48 columns, not 64, which this instantiation requires;
+    # an alpha other than Elu's default, so that a kernel ignoring it fails)
+    "wide_pro_512_4": dict(dims=(48, 512, 512, 512, 12), seed=41, head=8.0,
+                           front=[("Sub", "vec"), ("Div", "vec"), ("Clip", -3.0, 2.5)],
+                           acts=[("Elu", {"alpha": 0.7})] * 3,
+                           head_act=("Tanh", {}), tail=[("Clip", -0.6, 0.8), ("Mul", 0.25)]),
+    # 63 -> 512 -> 512 -> 16 (the widest observation and head the kernel takes): <3, 8, 16, 1>
+    "wide_pro_512_3": dict(dims=(63, 512, 512, 16), seed=42, head=8.0,
+                           front=[("Sub", "scalar"), ("Div", "scalar"), ("Mul", "vec")],
+                           acts=[("Selu", {"alpha": 1.2, "gamma": 0.8}), ("Clip", -1.0, 1.5)],
+                           head_act=("HardSigmoid", {"alpha": 0.3, "beta": 0.4}), tail=[]),
+    # 17 -> 256 -> 256 -> 1: <3, 4, 16, 1>
+    "wide_pro_256_3": dict(dims=(17, 256, 256, 1), seed=43, head=8.0, const_nodes=True,
+                           front=[("Mul", "vec"), ("Clip", -2.5, 2.0)],
+                           acts=[("LeakyRelu", {"alpha": 0.1}), ("Softplus", {})],
+                           head_act=None, tail=[]),
+    # 60 -> 256^3 -> 12: <4, 4, 16, 1>
+    "wide_pro_256_4": dict(dims=(60, 256, 256, 256, 12), seed=44, head=8.0,
+                           front=[("Sub", "vec"), ("Div", "vec"), ("Clip", -2.0, 3.0)],
+                           acts=[("Sigmoid", {}), ("Selu", {}), ("Clip", -1.0, 1.5)],
+                           head_act=None, tail=[("Clip", -0.5, 0.7), ("Mul", 0.5)]),
+    # no front-end, Elu: one shape on each side of every edge of the kernel's selection
+    # predicate (resident_wide.hip wide_shape)
+    "wide_edge_in63_out16": dict(dims=(63, 512, 512, 16), seed=45),     # the last shape inside
+    "wide_edge_in64": dict(dims=(64, 512, 512, 12), seed=46),           # in_dim 64
+    "wide_edge_k49_512_4": dict(dims=(49, 512, 512, 512, 12), seed=47),  # K_pad 64 with four layers of 512
+    "wide_edge_out17": dict(dims=(48, 512, 512, 17), seed=48),          # the head pads to 32
+    "wide_edge_5_layers": dict(dims=(48, 256, 256, 256, 256, 12), seed=49),
+    # the BASELINE shape with a different alpha per layer: not the 4-wave pipeline's, so its
+    # observation is padded to 64 columns, which four layers of 512 cannot take
+    "wide_edge_mixed_512_4": dict(dims=(48, 512, 512, 512, 12), seed=50,
+                                  acts=[("Elu", {"alpha": 1.0}), ("Elu", {"alpha": 0.6}), ("Elu", {"alpha": 1.4})]),
+}
+WIDE_VARIANTS = ["wide_pro_512_4", "wide_pro_512_3", "wide_pro_256_3", "wide_pro_256_4"]
+WIDE_NAN_VARIANTS = ["wide_pro_512_4", "wide_pro_256_4"]
+WIDE_EDGES = ["wide_edge_in63_out16", "wide_edge_in64", "wide_edge_k49_512_4", "wide_edge_out17",
+              "wide_edge_5_layers", "wide_edge_mixed_512_4"]
+# the tail's bounds of the graphs that have one, in output units before the trailing Mul
+# (wide_pro_512_3: the HardSigmoid head saturates at 0 and 1)
+WIDE_TAIL_BOUNDS = {"wide_pro_512_4": (-0.6, 0.8, 0.25), "wide_pro_512_3": (0.0, 1.0, 1.0),
+                    "wide_pro_256_4": (-0.5, 0.7, 0.5)}
+# the batch schedule of the wide-policy tests: B = 1 after B = 8 meets stale rows in the
+# kernel's LDS; B = 1 takes the per-lane prologue constants, B >= 2 the sweep path
+WIDE_SCHEDULE = [1, 8, 1, 2, 7, 1, 3, 8, 1] * 2
+
+
+def wide_spec(kind):
+    return _WIDE[kind]
+
+
+def wide_front_consts(kind):
+    """The front-end's constants, in the order of the spec's ops (a Clip: its bounds)."""
+    from go2_onnx_controller_amd import synth
+    s = _WIDE[kind]
+    K, out = s["dims"][0], []
+    for i, op in enumerate(s.get("front", [])):
+        if op[0] == "Clip":
+            out.append((np.float32(op[1]), np.float32(op[2])))
+        elif op[0] == "Sub":
+            out.append(synth.uniform(s["seed"], 900 + i, (K,) if op[1] == "vec" else (), 0.5))
+        else:  # Div / Mul: [0.5, 1.5], away from 0 and from 1
+            out.append((np.float32(1.0) + synth.uniform(s["seed"], 900 + i, (K,) if op[1] == "vec" else (), 0.5))
+                       .astype(np.float32))
+    return out
+
+
+def wide_bytes(kind: str) -> bytes:
+    from go2_onnx_controller_amd import synth
+    s = _WIDE[kind]
+    dims, seed = s["dims"], s["seed"]
+    layers = synth.mlp_layers(dims, seed)
+    hs = np.float32(s.get("head", 1.0))
+    layers[-1] = ((layers[-1][0] * hs).astype(np.float32), (layers[-1][1] * hs).astype(np.float32))
+    nodes, inits, cur = [], [], "obs"
+
+    def const(name, value):
+        value = np.asarray(value, np.float32)
+        if s.get("const_nodes"):
+            nodes.append(ow.node("Constant", [], [name], "", [ow.attr_tensor("value", value)]))
+        else:
+            inits.append((name, value))
+        return name
+
+    def clip(x, lo, hi, tag):
+        out = f"{tag}_out"
+        nodes.append(ow.node("Clip", [x, const(f"{tag}_lo", lo), const(f"{tag}_hi", hi)], [out]))
+        return out
+
+    for i, (op, c) in enumerate(zip(s.get("front", []), wide_front_consts(kind))):
+        if op[0] == "Clip":
+            cur = clip(cur, c[0], c[1], f"pre{i}")
+        else:
+            nodes.append(ow.node(op[0], [cur, const(f"pre{i}_k", c)], [f"pre{i}_out"]))
+            cur = f"pre{i}_out"
+    nh = len(layers) - 1
+    acts = s.get("acts", [("Elu", {"alpha": 1.0})] * nh)
+    for l, (W, b) in enumerate(layers):
+        inits += [(f"W{l}", W), (f"b{l}", b)]
+        nodes.append(ow.node("Gemm", [cur, f"W{l}", f"b{l}"], [f"g{l}"], "", [ow.attr_int("transB", 1)]))
+        cur = f"g{l}"
+        a = acts[l] if l < nh else s.get("head_act")
+        if a is None:
+            continue
+        if a[0] == "Clip":
+            cur = clip(cur, a[1], a[2], f"a{l}")
+        else:
+            nodes.append(ow.node(a[0], [cur], [f"a{l}_out"], "", [ow.attr_float(k, v) for k, v in a[1].items()]))
+            cur = f"a{l}_out"
+    for i, op in enumerate(s.get("tail", [])):
+        if op[0] == "Clip":
+            cur = clip(cur, op[1], op[2], f"post{i}")
+        else:
+            nodes.append(ow.node("Mul", [cur, const(f"post{i}_k", op[1])], [f"post{i}_out"]))
+            cur = f"post{i}_out"
+    nodes.append(ow.node("Identity", [cur], ["act"]))
+    return ow.model(nodes, inits, [("obs", ["N", dims[0]])], [("act", ["N", dims[-1]])])
+
+
+def wide_inputs(kind, schedule=None, seed=0):
+    """The observations of the wide-policy tests, one array per request of the schedule:
+    x = 2 N(0, 1), so that a front-end Clip binds on both sides."""
+    r = _rng(1000 + seed + _WIDE[kind]["seed"])
+    K = _WIDE[kind]["dims"][0]
+    return [(2.0 * r.standard_normal((B, K))).astype(np.float32) for B in (schedule or WIDE_SCHEDULE)]
+
+
+def wide_front(kind, x):
+    """The front-end of `kind` applied to x in float64, before its Clip (None: it has no
+    Clip), and the Clip's bounds."""
+    v, bounds = np.asarray(x, np.float64), None
+    for op, c in zip(_WIDE[kind].get("front", []), wide_front_consts(kind)):
+        if op[0] == "Clip":
+            bounds = (float(c[0]), float(c[1]))
+        elif op[0] == "Sub":
+            v = v - np.asarray(c, np.float64)
+        elif op[0] == "Div":
+            v = v / np.asarray(c, np.float64)
+        else:
+            v = v * np.asarray(c, np.float64)
+    return (v, bounds) if bounds else (None, None)
+
+
+def wide_tail_counts(kind, want):
+    """(outputs at the tail's lower bound, at its upper bound, strictly inside) of the
+    fp64 oracle's answer `want` (the bounds as the graph stores them: float32)."""
+    lo, hi, k = (np.float64(np.float32(v)) for v in WIDE_TAIL_BOUNDS[kind])
+    return int((want == lo * k).sum()), int((want == hi * k).sum()), int(((want > lo * k) & (want < hi * k)).sum())
+
+
 UNSUPPORTED = {
     # op the loader must reject with a clear message (no silent fallback)
     "conv": lambda: ow.model([ow.node("Conv", ["obs", "W"], ["act"])],
@@ -261,6 +428,7 @@ def _chain(mid_ops, tail=()):
 
 def write(tmp_path, kind, seed=0):
     p = tmp_path / f"{kind}.onnx"
-    data = variant_bytes(kind, seed) if kind in VARIANTS else UNSUPPORTED[kind]()
+    data = (variant_bytes(kind, seed) if kind in VARIANTS else wide_bytes(kind) if kind in _WIDE
+            else UNSUPPORTED[kind]())
     p.write_bytes(data)
     return str(p)

@@ -125,6 +125,78 @@ def test_loader_graph_variants(tmp_path, kind):
         assert v["pre_clip"] == pytest.approx([-1.2, 1.1])
 
 
+@pytest.mark.parametrize("kind", graphs.WIDE_VARIANTS + graphs.WIDE_EDGES)
+def test_loader_wide_graphs(tmp_path, kind):
+    """The wide-policy graphs of test_gpu_resident_wide.py load: dims, per-layer activations
+    and their attributes as the oracle's decoder sees them, the front-end's constants per
+    feature or as one broadcast scalar, the output tail."""
+    from go2_onnx_controller_amd import engine
+    p = graphs.write(tmp_path, kind)
+    v = engine.inspect_model(p)
+    s = graphs.wide_spec(kind)
+    _check_layers(v, _oracle_layers(p))
+    assert (v["in_dim"], v["out_dim"]) == (s["dims"][0], s["dims"][-1])
+    assert [l["N"] for l in v["layers"]] == list(s["dims"][1:])
+    size = {"vec": s["dims"][0], "scalar": 1}
+    front = {op[0]: op for op in s.get("front", [])}
+    for name in ("Sub", "Div", "Mul"):
+        assert v["pre_" + name.lower()] == (size[front[name][1]] if name in front else 0), name
+    if "Clip" in front:
+        assert v["pre_clip"] == pytest.approx(list(front["Clip"][1:]))
+    else:
+        assert v["pre_clip"] == [-1e308, 1e308]
+    tail = {op[0]: op for op in s.get("tail", [])}
+    if "Clip" in tail and s["head_act"] is None:  # a Clip right after the last Gemm: the head's activation
+        h = v["layers"][-1]
+        assert (h["act"], h["alpha"], h["beta"]) == (6, pytest.approx(tail["Clip"][1]), pytest.approx(tail["Clip"][2]))
+        assert v["clip"] == [-1e308, 1e308]
+    else:
+        assert v["clip"] == (pytest.approx(list(tail["Clip"][1:])) if "Clip" in tail else [-1e308, 1e308])
+    assert v["post_scale"] == (tail["Mul"][1] if "Mul" in tail else 1.0)
+    if kind == "wide_pro_512_3":  # every layer its own attributes
+        assert [(l["act"], l["alpha"], l["beta"]) for l in v["layers"]] == [
+            (7, pytest.approx(1.2), pytest.approx(0.8)), (6, -1.0, 1.5), (9, pytest.approx(0.3), pytest.approx(0.4))]
+    if kind == "wide_pro_512_4":
+        assert [(l["act"], l["alpha"]) for l in v["layers"][:3]] == [(1, pytest.approx(0.7))] * 3
+        assert v["layers"][3]["act"] == 3
+
+
+@pytest.mark.parametrize("kind", graphs.WIDE_VARIANTS + graphs.WIDE_EDGES)
+def test_wide_graph_inputs_bind(tmp_path, kind):
+    """The conditions the GPU tests of the wide-policy graphs rest on, checked on their own
+    inputs (graphs.wide_inputs: x = 2 N(0, 1) over graphs.WIDE_SCHEDULE, and the batches 5
+    and 300 of the other forms):
+
+    * the oracle evaluated in float32 is within the 1e-5 the GPU is held to (measured over
+      all of them: 3.2e-7 wide_pro_512_4, 7.8e-7 wide_pro_512_3, 1.5e-6 wide_pro_256_3,
+      whose one output reaches |4|, 8.4e-7 wide_pro_256_4, <= 7.7e-7 the edge shapes; over
+      the batch <= 8 schedule alone 2.3e-7, 5.3e-7, 9.8e-7, 6.5e-7, <= 3.0e-7);
+    * at every batch-8 request each output tail has at least two outputs at each bound and
+      at least a quarter strictly inside (measured, of 96 / 128 outputs: wide_pro_512_4
+      16-24 at -0.6, 8-14 at 0.8, 62-68 inside; wide_pro_512_3 13-27 at 0, 4-15 at 1,
+      89-110 inside; wide_pro_256_4 21-27 at -0.5, 28-33 at 0.7, 36-47 inside);
+    * at every batch-8 request each front-end Clip clips at least one element per bound
+      (measured: 7-112 below, 14-52 above)."""
+    from oracle import onnx_ref
+    g = onnx_ref.load(graphs.write(tmp_path, kind))
+    worst, n8 = 0.0, 0
+    for x in graphs.wide_inputs(kind) + graphs.wide_inputs(kind, [1, 5], seed=1) + graphs.wide_inputs(kind, [300], seed=2):
+        want = onnx_ref.act(g, x.astype(np.float64))
+        worst = max(worst, float(np.abs(onnx_ref.act(g, x, dtype=np.float32) - want).max()))
+        if x.shape[0] != 8:
+            continue
+        n8 += 1
+        if kind in graphs.WIDE_TAIL_BOUNDS:
+            lo, hi, inside = graphs.wide_tail_counts(kind, want)
+            assert lo >= 2 and hi >= 2 and 4 * inside >= want.size, (lo, hi, inside)
+        v, bounds = graphs.wide_front(kind, x)
+        if bounds:
+            assert (v < bounds[0]).any() and (v > bounds[1]).any()
+    print(f"{kind}: fp32 oracle within {worst:.2e} of fp64")
+    assert worst <= 1e-5
+    assert n8 == 4
+
+
 @pytest.mark.parametrize("kind,msg", [("conv", "unsupported operator 'Conv'"),
                                       ("dynamic_weight", "not an initializer"),
                                       ("clip_after_act_mid", "only supported at the end of the graph"),

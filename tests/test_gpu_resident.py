@@ -470,6 +470,95 @@ def test_resident_lstm_idle_exit_keeps_state(synth_path):
         assert abs_err(r.get_hidden(8), hc_ref) <= TOL
 
 
+@pytest.mark.parametrize("form", ["act1", "wide", "multi", "ctl", "gru_128", "lstm_128", "launch_shipped",
+                                  "launch_mlp512"])
+def test_tag_space_wrap(synth_path, form, monkeypatch):
+    """The 32-bit tag space runs out and restarts (engine.cpp resident_serve / resident_ready /
+    next_epoch): GO2PI_EPOCH0 starts the engine just below the wrap, which a deployed 1 kHz
+    policy meets after about 8 days.
+
+    Resident forms, GO2PI_EPOCH0 = 0xFFFFFF00: a request takes span = nl + 2 tags (2 <= nl
+    <= 6 here, so 4 <= span <= 8) and the engine restarts once epoch > 0xFFFFFFF0 - 2 span,
+    that is after ceil((0xF0 - 2 span + 1) / span) requests: 59 at span 4, 28 at span 8. So
+    the wrap falls inside 120 requests for every form, and once (120 more requests move the
+    epoch by < 1000). resident_launches == 2 (the first launch and the relaunch at the wrap;
+    resident_ms = 5000 keeps any other relaunch out) shows the branch ran, and ran once.
+    Launch per call (resident_ms = 0), nl = 4: a call takes nl tags and the restart comes
+    once epoch > 0xFFFFFFFF - 2 nl = 0xFFFFFFF7; from GO2PI_EPOCH0 = 0xFFFFFFD0 calls 1-10
+    take 0xD0 .. 0xF4 and call 11 starts over at 1.
+
+    Every answer before and after is within 1e-5 of the fp64 oracle (the controller tick by
+    test_gpu_controller.py's checks: observation rows bit-exact, actions and outputs as
+    there). GRU / LSTM: the rollout per row, so the hidden (and cell) rows are continuous
+    across the stop and relaunch, and get_hidden at the end matches the oracle's state.
+    Measured on an MI355X: worst |y - oracle| 3.7e-7 (the shipped model), hidden rows 1.1e-7."""
+    from go2_onnx_controller_amd import Engine
+    from oracle import mlp_ref, onnx_ref
+    launch = form.startswith("launch")
+    monkeypatch.setenv("GO2PI_EPOCH0", "0xFFFFFFD0" if launch else "0xFFFFFF00")  # read at engine creation
+    if form == "multi":
+        monkeypatch.setenv("GO2PI_RES_MULTI", "1")
+    rng = np.random.default_rng(53)
+    n_req = 120
+    worst = 0.0
+    if form == "ctl":
+        from test_gpu_controller import _mlp_policy, _run_ticks
+        with Engine(SHIPPED, max_batch=8, resident_ms=5000) as e:
+            assert e.resident_kernel.startswith("policy_act1_kernel")
+            for k in range(8):  # 8 x 15 ticks, B = 1 and 8 alternating
+                _run_ticks(e, _mlp_policy(SHIPPED), 1 if k % 2 == 0 else 8, 15, seed=70 + k)
+            assert e.resident_launches == 2
+        return
+    if form in ("gru_128", "lstm_128"):
+        p = synth_path(form)
+        g = onnx_ref.load(p)
+        lstm = form.startswith("lstm")
+        with Engine(p, max_batch=8, resident_ms=5000) as e:
+            assert e.resident_kernel.startswith("policy_resident_kernel")
+            S = e.hidden_dim  # GRU: H; LSTM: 2H (h | c)
+            H = S // 2 if lstm else S
+            s_ref = np.zeros((8, S))
+            e.reset_hidden()
+            for i in range(n_req):
+                B = [1, 8, 2, 1, 5, 3][i % 6]
+                x = rng.standard_normal((B, e.in_dim)).astype(np.float32)
+                feeds = {"observation": x.astype(np.float64), "h_in": s_ref[None, :B, :H]}
+                if lstm:
+                    feeds["c_in"] = s_ref[None, :B, H:]
+                r = onnx_ref.run(g, feeds)
+                s_ref[:B] = np.concatenate([r["h_out"][0], r["c_out"][0]], axis=1) if lstm else r["h_out"][0]
+                err = abs_err(e.run(x), r["action"])
+                worst = max(worst, err)
+                assert err <= TOL, f"request {i} B={B}: {err:.3e}"
+            launches = e.resident_launches
+            h_err = abs_err(e.get_hidden(8), s_ref)
+        print(f"{form}: worst |y - oracle| {worst:.3e}, hidden rows {h_err:.3e}, {launches} launches")
+        assert h_err <= TOL
+        assert launches == 2
+        return
+    path = SHIPPED if form in ("act1", "launch_shipped") else synth_path("go2_mlp_512")
+    ref = mlp_ref.MlpRef.from_onnx(path)
+    want_kernel = {"act1": "policy_act1_kernel", "wide": "policy_wide_kernel", "multi": "policy_resident_kernel"}
+    with Engine(path, max_batch=8, resident_ms=0 if launch else 5000) as e:
+        if launch:
+            assert e.cost["n_layers"] == 4 and e.resident_kernel == "none"
+            n_req = 24
+        elif form == "wide" and e.resident_kernel.endswith("ring=host"):
+            assert e.resident_kernel.startswith("policy_resident_kernel")  # (no large BAR: the multi-workgroup form)
+        else:
+            assert e.resident_kernel.startswith(want_kernel[form]), e.resident_kernel
+        for i in range(n_req):
+            B = [1, 8][i % 2] if launch else [1, 8, 1, 3, 1, 5][i % 6]
+            x = (realistic_obs(B, seed=300 + i) if path == SHIPPED
+                 else rng.standard_normal((B, e.in_dim)).astype(np.float32))
+            err = abs_err(e.run(x), ref.f64(x))
+            worst = max(worst, err)
+            assert err <= TOL, f"request {i} B={B}: {err:.3e}"
+        launches = e.resident_launches
+    print(f"{form}: worst |y - oracle| {worst:.3e}, {launches} launches")
+    assert launches == (0 if launch else 2)
+
+
 def test_batched_launch_evicts_other_resident_kernels(synth_path):
     """A batched launch on the device tells other engines' live resident kernels to
     leave (they hold CUs the launch needs: DESIGN §4.2b); the evicted engine's act()
