@@ -224,6 +224,40 @@ inline __device__ __noinline__ void ln_rows(float *X, int stride, int r0, int r1
   }
 }
 
+// ln_rows' register path for a kernel that holds the layer's Scale / B itself and has no
+// registers for a call (policy_act1_kernel: its lanes carry the policy's weights): U
+// columns per lane (N <= 64 U), g / b the lane's Scale and B of columns lane + 64 u (0 past
+// N), inlined. The additions run in ln_rows' order (the lane's columns ascending, wave_sum,
+// the variance of x - mean in a second pass, 1 / sqrt, fmaf(x * rstd, g, b), then the
+// activation's own arithmetic), so a row's result is the bits ln_rows gives.
+template <int U>
+__device__ __forceinline__ void ln_rows_held(float *X, int stride, int r0, int r1, int rs, const float (&g)[U],
+                                             const float (&b)[U], int N, float eps, ActP ap, int lane) {
+  lds_float *Xl = (lds_float *)X;
+  const float fn = (float)N;
+  for (int r = r0; r < r1; r += rs) {
+    lds_float *row = Xl + r * stride;
+    float x[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) x[u] = lane + 64 * u < N ? row[lane + 64 * u] : 0.f;
+    float s = 0.f;
+#pragma unroll
+    for (int u = 0; u < U; ++u) s += x[u];
+    const float mean = wave_sum(s) / fn;
+    float v = 0.f;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const float d = lane + 64 * u < N ? x[u] - mean : 0.f;
+      x[u] = d;
+      v = fmaf(d, d, v);
+    }
+    const float rstd = 1.f / sqrtf(wave_sum(v) / fn + eps);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (lane + 64 * u < N) row[lane + 64 * u] = act_fn(ap.act, ap.alpha, ap.beta, fmaf(x[u] * rstd, g[u], b[u]));
+  }
+}
+
 // The action epilogue (go2pi_opts and a graph's trailing Clip / scalar Mul):
 // y <- scale * clip(tanh?(y), lo, hi); the clip passes a NaN through, as ONNX Clip.
 // Post: its program fields read once, by value — a loop that stores the actions

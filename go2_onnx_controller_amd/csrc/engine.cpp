@@ -748,7 +748,9 @@ void set_ctl_params(go2pi_engine &e, const go2pi_ctl_params &cp) {
 }
 
 // A policy with a LayerNormalization on any layer: served by the general batched body
-// and the GEMV chain only (no pipeline / lean kernel, latency kernel or resident form).
+// and the GEMV chain only (no pipeline / lean kernel, latency kernel or resident form);
+// with opts.ln_small = 1 a dense one also by the latency kernel and, of the resident
+// forms, policy_act1_kernel's act() form or the multi-workgroup kernel (ln_small_on).
 bool has_ln(const go2pi::Model &m) {
   for (const auto &d : m.layers)
     if (d.ln) return true;
@@ -775,6 +777,9 @@ bool w4_eligible(const go2pi_engine &e, const go2pi::Model &m) {
       return false;
   return true;
 }
+
+// opts.ln_small: exactly 1 turns it on (the field fills the earlier layout's tail padding)
+bool ln_small_on(const go2pi_engine &e) { return e.opts.ln_small == 1; }
 
 void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o) {
   go2pi_default_opts(&e.opts);
@@ -1014,13 +1019,23 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
     for (int l = 0; l < p.nl; ++l) kmax = std::max(kmax, p.L[l].K_pad);
     const bool lat_shape = kmax <= 1024 && go2pi::latency_grid(p) <= 256 && e.small_batch > 0 &&
                            !std::getenv("GO2PI_SMALL_CHAIN");  // env: diagnostics, force the GEMV chain
-    e.latency_ok = !m.has_gru && lat_shape && !has_ln(m);
+    // (a LayerNormalization policy: only with opts.ln_small; latency_body normalises the
+    // swept rows as gemv_layer_kernel does)
+    const bool ln = has_ln(m);
+    e.latency_ok = !m.has_gru && lat_shape && (!ln || ln_small_on(e));
+    // a layer past the first with more than 512 input columns: at batch 5 and up its input
+    // rows pass the 4096 granules one sweep round takes. The single launch and the
+    // resident act() form sweep a second round (their general instantiations,
+    // program.hpp program_small_general); the resident controller and recurrent forms do not
+    int kmax1 = 0;
+    for (int l = 1; l < p.nl; ++l) kmax1 = std::max(kmax1, p.L[l].K_pad);
+    const bool one_round = kmax1 <= 512;
     // the resident kernel's GRU / LSTM form (resident.hip, RNN): the cell tiled in front
     // of the dense layers, h' carried between requests as granules (an LSTM's c in the
     // owning workgroups' LDS)
     const bool res_rnn = m.has_gru && ((m.gru.cell == 0 && m.gru.lbr == 1) || m.gru.cell == 1) && m.gru.H % 64 == 0 &&
                          p.gru.I_pad + m.gru.H <= 512 && (m.gru.H >> 4) <= 256 && lat_shape && e.opts.resident_ms > 0 &&
-                         !has_ln(m);
+                         !ln && one_round;
     e.palloc(&e.h_err, &e.m_err, 512);
     p.err = e.m_err + 64;  // batched kernel hand-off timeouts
     if (e.latency_ok || res_rnn) {
@@ -1054,7 +1069,9 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
       e.res_idle_ticks = (unsigned long long)e.opts.resident_ms * (unsigned long long)khz;
       e.resident_ok = true;
       res_register(&e);
-      e.resident_ctl_ok = !m.has_gru;  // the controller-tick form serves dense policies
+      // the controller-tick form serves dense policies without LayerNormalization (an LN
+      // policy's tick at batch <= 8: policy_latency_ctl_kernel)
+      e.resident_ctl_ok = !m.has_gru && !ln && one_round;
     }
   }
   // GO2PI_EPOCH0=<u32>: the engine's first granule tag instead of 1 (diagnostics and tests: a
@@ -1135,6 +1152,13 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   // the multi-workgroup form, A/B diagnostics)
   e.resident1 = e.resident_ok && !m.has_gru && go2pi::resident1_fits(p, false) && !std::getenv("GO2PI_RES_MULTI");
   e.resident1_ctl = e.resident_ok && !m.has_gru && go2pi::resident1_fits(p, true) && !std::getenv("GO2PI_RES_MULTI");
+  // a LayerNormalization policy (opts.ln_small): policy_act1_kernel's act() form where its
+  // shape applies, never r04's policy_resident1_kernel (also under GO2PI_RES_R1W=1, which
+  // then selects the multi-workgroup form) and no single-workgroup controller form
+  if (has_ln(m)) {
+    e.resident1 = e.resident_ok && go2pi::resident1_ctl_granules(p) && !std::getenv("GO2PI_RES_MULTI");
+    e.resident1_ctl = false;
+  }
   e.ctl_gran_ok = e.resident1_ctl && go2pi::resident1_ctl_granules(p);
   // the controller tick's general body instead of the lean tick kernel (A/B diagnostics,
   // tests/test_gpu_controller.py::test_controller_tick_bodies)
@@ -1144,8 +1168,8 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   // request ring in device memory (large BAR); else by the multi-workgroup kernel, whose
   // workgroup 0 alone polls the host and mirrors the request (GO2PI_RES_MULTI=1: that
   // form regardless, A/B and its tests)
-  e.wide = e.resident_ok && !e.resident1 && !m.has_gru && e.req_bar_bytes > 0 && go2pi::wide_shape(p).nl > 0 &&
-           !std::getenv("GO2PI_RES_MULTI");
+  e.wide = e.resident_ok && !e.resident1 && !m.has_gru && !has_ln(m) && e.req_bar_bytes > 0 &&
+           go2pi::wide_shape(p).nl > 0 && !std::getenv("GO2PI_RES_MULTI");
   hip_check(go2pi::configure_kernels(p, e.waves), "hipFuncSetAttribute");
   e.d_prog = e.dalloc<go2pi::DevProgram>(1);
   hip_check(hipMemcpy(e.d_prog, &p, sizeof(p), hipMemcpyHostToDevice), "hipMemcpy");
@@ -1236,6 +1260,7 @@ void go2pi_default_opts(go2pi_opts *o) {
   o->action_tanh = 0;
   o->action_clip = 0.f;
   o->action_scale = 0.f;
+  o->ln_small = 0;
 }
 
 int go2pi_create_from_memory(const void *bytes, size_t nbytes, const go2pi_opts *opts, go2pi_engine **out) {
@@ -1782,6 +1807,20 @@ int go2pi_resident_kernel(const go2pi_engine *e, char *buf, size_t cap) {
     } else {
       std::snprintf(buf, cap, "policy_resident_kernel%s", ring);
     }
+    return GO2PI_OK;
+  });
+}
+
+int go2pi_small_kernel(const go2pi_engine *e, char *buf, size_t cap) {
+  // (go2pi_run's selection at batch <= GO2PI_SMALL_MAXB: use_latency, use_graph, use_chain)
+  if (e && buf && cap && !e->latency_ok && !e->use_chain(1)) return go2pi_batched_kernel(e, buf, cap);
+  return guarded([&] {
+    check_engine(e);
+    if (!buf || cap == 0) throw ApiError("null buffer", GO2PI_E_INVALID);
+    if (e->latency_ok)  // (an LN program's instantiation of it: policy_latency_ln_kernel)
+      std::snprintf(buf, cap, "policy_latency_kernel");
+    else
+      std::snprintf(buf, cap, e->opts.use_graph ? "gemv_layer_kernel graph" : "gemv_layer_kernel");
     return GO2PI_OK;
   });
 }

@@ -175,7 +175,10 @@ __device__ __forceinline__ bool sweep_layer(unsigned long long *gran, int n, uns
 // workgroup 0 (the only one of the one-tile final layer, so every other
 // workgroup's reads of the previous obs / action are done by then) writes the
 // new observation and status before signalling completion.
-template <bool CTL>
+// LNORM: the general instantiation (program.hpp program_small_general): the LayerNormalization
+// pass (opts.ln_small) and a second sweep round for layer inputs of more than 4096
+// granules. Every other program runs the instantiation without either.
+template <bool CTL, bool LNORM = false>
 __device__ __forceinline__ void latency_body(const DevProgram &P, const float *obs, float *act, int B,
                                              unsigned epoch0, unsigned long long *gran, int gstride, unsigned *err,
                                              unsigned *done, const DevCtl ctl) {
@@ -227,12 +230,30 @@ __device__ __forceinline__ void latency_body(const DevProgram &P, const float *o
       // every wave sweeps its own 512 granules (8 per lane, all in flight), not
       // wave 0 alone in B * K_pad / 512 serial rounds
       const int n = B * K_pad, lo = wave * 512;
-      if (lo < n && !sweep_layer(gran + (size_t)(l - 1) * gstride + lo, min(512, n - lo), epoch0 + (unsigned)(l - 1),
-                                 xs + lo, err, lane))
+      unsigned long long *gl = gran + (size_t)(l - 1) * gstride;
+      if (lo < n && !sweep_layer(gl + lo, min(512, n - lo), epoch0 + (unsigned)(l - 1), xs + lo, err, lane))
         abort_flag = 1;
+      // rows past the eight waves' 4096 granules (K_pad > 512 at batch 5 and up; K_pad <= 1024
+      // and B <= 8: at most 8192): a second round
+      if constexpr (LNORM) {
+        if (n > LAT_WAVES * 512) {  // uniform over the workgroup
+          const int lo2 = lo + LAT_WAVES * 512;
+          if (lo2 < n && !sweep_layer(gl + lo2, min(512, n - lo2), epoch0 + (unsigned)(l - 1), xs + lo2, err, lane))
+            abort_flag = 1;
+        }
+      }
     }
     __syncthreads();
     if (abort_flag) return;
+    // The previous layer's LayerNormalization, as in gemv_layer_kernel: the granules carry
+    // its un-normalised output (a pre-LN layer's act is none), every consumer workgroup
+    // swept the whole rows, so each normalises its own copy, one row per wave.
+    if constexpr (LNORM) {
+      if (l > 0 && P.L[l - 1].ln) {  // uniform over the workgroup
+        ln_rows(xs, K_pad, wave, B, LAT_WAVES, ln_of(P.L[l - 1]), lane);
+        __syncthreads();
+      }
+    }
     float p[GO2PI_SMALL_MAXB];
 #pragma unroll
     for (int b = 0; b < GO2PI_SMALL_MAXB; ++b) p[b] = 0.f;
@@ -322,6 +343,21 @@ __global__ __launch_bounds__(LAT_WAVES * 64) void policy_latency_ctl_kernel(cons
   latency_body<true>(*Pd, nullptr, nullptr, B, epoch0, gran, gstride, err, done, C);
 }
 
+// ... and the general instantiations (the LN pass, the second sweep round)
+__global__ __launch_bounds__(LAT_WAVES * 64) void policy_latency_ln_kernel(const DevProgram *__restrict__ Pd,
+                                                                           const float *obs, float *act, int B,
+                                                                           unsigned epoch0, unsigned long long *gran,
+                                                                           int gstride, unsigned *err, unsigned *done) {
+  latency_body<false, true>(*Pd, obs, act, B, epoch0, gran, gstride, err, done, DevCtl{});
+}
+
+__global__ __launch_bounds__(LAT_WAVES * 64) void policy_latency_ctl_ln_kernel(const DevProgram *__restrict__ Pd,
+                                                                               DevCtl C, int B, unsigned epoch0,
+                                                                               unsigned long long *gran, int gstride,
+                                                                               unsigned *err, unsigned *done) {
+  latency_body<true, true>(*Pd, nullptr, nullptr, B, epoch0, gran, gstride, err, done, C);
+}
+
 int latency_grid(const DevProgram &p) {
   int grid = 1;
   for (int l = 0; l < p.nl; ++l) grid = std::max(grid, p.L[l].N_pad >> 4);
@@ -336,9 +372,9 @@ int launch_latency(const DevProgram &p, const DevProgram *p_dev, const float *ob
   const int grid = latency_grid(p);
   const size_t lds =
       sizeof(float) * ((size_t)GO2PI_SMALL_MAXB * p.lds_stride + LAT_WAVES * GO2PI_SMALL_MAXB * 16 + 4);
-  hipLaunchKernelGGL(policy_latency_kernel, dim3(grid), dim3(LAT_WAVES * 64), lds,
-                     reinterpret_cast<hipStream_t>(stream), p_dev, obs, act, batch, epoch0, gran, gstride, err,
-                     done);
+  hipLaunchKernelGGL(program_small_general(p) ? policy_latency_ln_kernel : policy_latency_kernel, dim3(grid),
+                     dim3(LAT_WAVES * 64), lds, reinterpret_cast<hipStream_t>(stream), p_dev, obs, act, batch, epoch0,
+                     gran, gstride, err, done);
   return (int)hipGetLastError();
 }
 
@@ -350,8 +386,9 @@ int launch_latency_ctl(const DevProgram &p, const DevProgram *p_dev, const DevCt
   const size_t lds = sizeof(float) * ((size_t)GO2PI_SMALL_MAXB * p.lds_stride + LAT_WAVES * GO2PI_SMALL_MAXB * 16 + 4 +
                                       (size_t)GO2PI_SMALL_MAXB * p.in_dim + GO2PI_SMALL_MAXB +
                                       ctl_lds_floats(GO2PI_SMALL_MAXB, p.in_dim));
-  hipLaunchKernelGGL(policy_latency_ctl_kernel, dim3(grid), dim3(LAT_WAVES * 64), lds,
-                     reinterpret_cast<hipStream_t>(stream), p_dev, ctl, batch, epoch0, gran, gstride, err, done);
+  hipLaunchKernelGGL(program_small_general(p) ? policy_latency_ctl_ln_kernel : policy_latency_ctl_kernel, dim3(grid),
+                     dim3(LAT_WAVES * 64), lds, reinterpret_cast<hipStream_t>(stream), p_dev, ctl, batch, epoch0, gran,
+                     gstride, err, done);
   return (int)hipGetLastError();
 }
 

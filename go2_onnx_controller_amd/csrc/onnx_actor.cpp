@@ -59,6 +59,9 @@ ONNXActor::ONNXActor(const std::string &model_path, const std::span<float> obser
   // without one (GO2PI_RESIDENT_MS overrides; 0 = one launch per call).
   opts.resident_ms = 100;
   if (const char *v = std::getenv("GO2PI_RESIDENT_MS")) opts.resident_ms = std::atoi(v);
+  // GO2PI_LN_SMALL=1: a LayerNormalization policy's act() takes the single-launch and
+  // resident kernels too (go2pi_opts.ln_small; off otherwise: one launch per layer)
+  if (const char *v = std::getenv("GO2PI_LN_SMALL")) opts.ln_small = std::atoi(v) == 1 ? 1 : 0;
   check(go2pi_create(model_path.c_str(), &opts, &impl_->engine), "cannot load model");
   impl_->input_name = name_of(impl_->engine, 0);
   impl_->output_name = name_of(impl_->engine, 1);

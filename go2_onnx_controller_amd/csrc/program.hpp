@@ -164,6 +164,24 @@ struct DevProgram {
   DevLayer L[GO2PI_MAX_LAYERS];
 };
 
+// a LayerNormalization on any layer (host side: which instantiation a launcher picks)
+inline bool program_has_ln(const DevProgram &p) {
+  for (int l = 0; l < p.nl; ++l)
+    if (p.L[l].ln) return true;
+  return false;
+}
+
+// The small-batch kernels' general instantiations (policy_latency_ln_kernel,
+// policy_resident_kernel<.., true>) serve a program with a LayerNormalization, and one
+// whose swept layer inputs can pass the 4096 granules the eight waves take in one round
+// (a layer past the first with K_pad > 512, at batch 5 and up): they sweep a second
+// round. Every other program runs the instantiations without either.
+inline bool program_small_general(const DevProgram &p) {
+  for (int l = 1; l < p.nl; ++l)
+    if (p.L[l].K_pad > 512) return true;
+  return program_has_ln(p);
+}
+
 // ---------------------------------------------------------------------------
 // Controller tick: the Go2 controller's observation
 // assembly (onnx_controller/src/controller.cpp:173-212, controller.hpp:45-68,

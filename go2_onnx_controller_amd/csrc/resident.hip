@@ -270,7 +270,11 @@ __device__ __forceinline__ void local_layer0(const DevProgram &P, const float4 (
 // them). A row not yet written in this launch comes from the engine's state rows
 // in HBM; each cell workgroup writes its units' latest h' back to those rows when
 // the kernel leaves (not while it runs: the rows are read then).
-template <int NF, bool CTL, int RNN = 0>
+// LNORM: the general instantiation (program.hpp program_small_general; act() form of a
+// dense policy only): the LayerNormalization pass on a layer's input (opts.ln_small) and
+// a second sweep round for layer inputs of more than 4096 granules. Every other program
+// runs the instantiations without either.
+template <int NF, bool CTL, int RNN = 0, bool LNORM = false>
 __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const DevProgram *__restrict__ Pd,
                                                                          const u64 *req, u64 *actg, u64 *gran,
                                                                          int gstride, u64 *mirror, unsigned *err,
@@ -278,6 +282,7 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
                                                                          u64 *hgran, float *hidden,
                                                                          const unsigned *yield) {
   static_assert(!(RNN && (NF > 0 || CTL)), "the GRU form tiles layer 0 and serves act() only");
+  static_assert(!(LNORM && (CTL || RNN)), "LayerNormalization: the dense act() form only");
   constexpr bool LOCAL0 = NF > 0;
   constexpr bool LSTM = RNN == 2;
   constexpr int NG = LSTM ? 4 : 3;  // gate fragments per (chunk, tile)
@@ -606,11 +611,22 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
         // every wave sweeps its own 512 granules (8 per lane, all in flight): at
         // batch 8 one wave's eight serial rounds cost ~20 us per call
         const int n = B * K_pad, lo = wave * 512;
+        const u64 *gl = gran + (size_t)(l - 1) * gstride;
         if (lo < n &&
-            sweep<__HIP_MEMORY_SCOPE_AGENT>(gran + (size_t)(l - 1) * gstride + lo, min(512, n - lo), e + (unsigned)l,
-                                            xs + lo, err, lane) != 1 &&
+            sweep<__HIP_MEMORY_SCOPE_AGENT>(gl + lo, min(512, n - lo), e + (unsigned)l, xs + lo, err, lane) != 1 &&
             lane == 0)
           st[0] = 1;
+        // rows past the eight waves' 4096 granules (K_pad > 512 at batch 5 and up; at most
+        // 8 x 1024): a second round
+        if constexpr (LNORM) {
+          if (n > RES_WAVES * 512) {  // uniform over the workgroup
+            const int lo2 = lo + RES_WAVES * 512;
+            if (lo2 < n &&
+                sweep<__HIP_MEMORY_SCOPE_AGENT>(gl + lo2, min(512, n - lo2), e + (unsigned)l, xs + lo2, err, lane) != 1 &&
+                lane == 0)
+              st[0] = 1;
+          }
+        }
       }
       __syncthreads();
 #ifdef GO2PI_DIAG_RESDBG
@@ -619,6 +635,17 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
       if (st[0]) {
         left = true;
         break;
+      }
+      // The previous layer's LayerNormalization (policy_latency_kernel's pass): xs holds its
+      // whole un-normalised rows behind the barrier above, swept from the granules or left
+      // by local_layer0 (whose last barrier the store of every row precedes), and no wave
+      // met a LEAVE tag (st[0], checked first: a half-swept row is never normalised into
+      // an answer). Each workgroup normalises its own copy, one row per wave.
+      if constexpr (LNORM) {
+        if (l > 0 && P.L[l - 1].ln) {  // uniform over the workgroup
+          ln_rows(xs, K_pad, wave, B, RES_WAVES, ln_of(P.L[l - 1]), lane);
+          __syncthreads();
+        }
       }
       if (l < 5) RES_STAMP(2 * l + 2);  // layer l's input ready
       float p[GO2PI_SMALL_MAXB];
@@ -1163,12 +1190,21 @@ __global__ __launch_bounds__(NT) void policy_resident1_kernel(const DevProgram *
 // (ctl_fn.hpp, the code of the batched kernel: the new rows go to the host staging, the
 // normalised ones to x0), run the layers, post-process the action into the staging
 // (ctl_store) and set the done word behind every output's drain.
-template <int NL, int H, int F0, unsigned AS, int D, bool PRO, int CW = 8, bool CTL = false>
+// LN: the program has LayerNormalization on wide layers (act() form, run-time
+// activations only). After wide layer l's barrier, where P.L[l].ln is set, compute wave w
+// normalises rows w, w + CW, ... < B of the layer's output in place (ln_rows_held: Scale
+// and B held in registers, H / 64 columns per lane, ln_rows' bits), then one more
+// barrier; the next layer or the head reads normalised rows. Barriers per request, the
+// request loop's top one included, for the polling wave and every compute wave alike
+// (both count from the same SGPR values lnm[l] = P.L[l].ln != 0):
+//   NL = 2: 2 + lnm[0]     NL = 3: 3 + lnm[0] + lnm[1]     NL = 4: 4 + lnm[0] + lnm[1] + lnm[2]
+template <int NL, int H, int F0, unsigned AS, int D, bool PRO, int CW = 8, bool CTL = false, bool LN = false>
 __global__ __launch_bounds__(a1_nt(CW)) void policy_act1_kernel(const DevProgram *__restrict__ Pd, const u64 *req,
                                                                 u64 *actg, unsigned *err, unsigned *done,
                                                                 u64 idle_ticks, const unsigned *yield, DevCtl C) {
   static_assert(NL >= 2 && NL <= 4 && (H == 64 || H == 128) && F0 >= 1 && F0 <= 4 && (CW == 4 || CW == 8),
                 "policy_act1_kernel shape");
+  static_assert(!LN || (!CTL && AS == 0xFFFFFFFFu), "LayerNormalization: the generic act() form only");
   constexpr int NT = a1_nt(CW);
   constexpr int R = H / (4 * CW);  // outputs per lane in a wide layer (a DPP row of 16 lanes: 16 R / 16)
   constexpr int HF = H / 64;  // float4s per lane of a K = H layer
@@ -1177,7 +1213,9 @@ __global__ __launch_bounds__(a1_nt(CW)) void policy_act1_kernel(const DevProgram
   // CTL: layer 0's and the head's weights live in LDS, not registers (re-read per request,
   // 8 + 2 ds_read_b128 per lane for the shipped model): beside the assembly's registers
   // they spilled
-  constexpr bool W0L = CTL;
+  // LN, four layers of 128: the same (the LN pass's registers beside all the weights
+  // spilled 7 to 33 registers to scratch)
+  constexpr bool W0L = CTL || (LN && H == 128 && NL == 4);
   const DevProgram &P = *Pd;
   extern __shared__ float4 lds4[];
   const int S = P.lds_stride;
@@ -1257,6 +1295,30 @@ __global__ __launch_bounds__(a1_nt(CW)) void policy_act1_kernel(const DevProgram
   const int post_tanh = ACT_RT ? r1_keep(P.post_tanh) : P.post_tanh;
   const float clo = ACT_RT ? r1_keep(P.clip_lo) : P.clip_lo, chi = ACT_RT ? r1_keep(P.clip_hi) : P.clip_hi;
   const float pscale = ACT_RT ? r1_keep(P.scale) : P.scale;
+  // LN: each wide layer's LayerNormalization, its scalars in SGPRs and the lane's Scale /
+  // B of columns lane + 64 u in registers for the kernel's life (0 where the layer has none)
+  constexpr int NLN = LN ? NL - 1 : 1;
+  [[maybe_unused]] int lnm[NLN], lnn[NLN], lnact[NLN];
+  [[maybe_unused]] float lneps[NLN], lnal[NLN], lnbe[NLN], lng[NLN][HF], lnb[NLN][HF];
+  if constexpr (LN) {
+#pragma unroll
+    for (int l = 0; l < NL - 1; ++l) {
+      const DevLayer &L = P.L[l];
+      lnm[l] = r1_keep(L.ln != 0 ? 1 : 0);
+      lnn[l] = r1_keep(L.N);
+      lnact[l] = r1_keep(L.ln_act);
+      lneps[l] = r1_keep(L.ln_eps);
+      lnal[l] = r1_keep(L.ln_alpha);
+      lnbe[l] = r1_keep(L.ln_beta);
+#pragma unroll
+      for (int u = 0; u < HF; ++u) {
+        const int k = lane + 64 * u;
+        const bool on = lnm[l] && k < lnn[l];
+        lng[l][u] = on ? L.ln_g[k] : 0.f;
+        lnb[l][u] = on ? L.ln_b[k] : 0.f;
+      }
+    }
+  }
   // the polling wave: each lane's prologue constants for its granule positions (the
   // column of granule i is (i - 1) mod in_dim whatever the batch)
   const Pro pro = PRO ? pro_of(P) : Pro{};
@@ -1332,7 +1394,12 @@ __global__ __launch_bounds__(a1_nt(CW)) void policy_act1_kernel(const DevProgram
     last = e;
     if (wave == 0) {  // the poller passes the request's barriers, then polls again
 #pragma unroll
-      for (int l = 0; l + 1 < NL; ++l) lds_barrier();
+      for (int l = 0; l + 1 < NL; ++l) {
+        lds_barrier();
+        if constexpr (LN) {
+          if (lnm[l]) lds_barrier();  // layer l's LayerNormalization pass (the compute waves' second barrier)
+        }
+      }
       if constexpr (CTL) {
         lds_barrier();  // the assembly
         lds_barrier();  // the outputs drained (the done word)
@@ -1438,6 +1505,13 @@ __global__ __launch_bounds__(a1_nt(CW)) void policy_act1_kernel(const DevProgram
       }
       if (l == 0) A1_CLOCK(64, 18);
       lds_barrier();
+      if constexpr (LN) {
+        if (lnm[l]) {  // uniform (an SGPR): the polling wave passes the same barrier
+          ln_rows_held<HF>(Y, S, wave - 1, B, CW, lng[l], lnb[l], lnn[l], lneps[l], ActP{lnact[l], lnal[l], lnbe[l]},
+                           lane);
+          lds_barrier();
+        }
+      }
       if (l < 6) A1_STAMP(64, 2 + l);
       if (l < 3) A1_CLOCK(64, 25 + l);
       X = Y;
@@ -1519,6 +1593,28 @@ int a1_generic_f0(int f0, GO &go1) {
   if constexpr (!(H == 128 && NL == 4)) return go1(policy_act1_kernel<NL, H, 4, 0xFFFFFFFFu, D4, true, 8>, 8);
   return (int)hipErrorInvalidValue;  // (act1_shape refuses it)
 }
+// ... of a LayerNormalization program (act() form; LN = true)
+template <int NL, int H, class GO>
+int a1_generic_ln_f0(int f0, GO &go1) {
+  constexpr int D2 = (H == 128 && NL == 4) ? 1 : 2;
+  if (f0 == 1) return go1(policy_act1_kernel<NL, H, 1, 0xFFFFFFFFu, 2, true, 8, false, true>, 8);
+  if (f0 == 2) return go1(policy_act1_kernel<NL, H, 2, 0xFFFFFFFFu, D2, true, 8, false, true>, 8);
+  // (H = 128, NL = 3, F0 = 4 spilled 28 registers with the LN pass: act1_shape refuses it too)
+  if constexpr (H != 128 || NL == 2)
+    return go1(policy_act1_kernel<NL, H, 4, 0xFFFFFFFFu, 2, true, 8, false, true>, 8);
+  return (int)hipErrorInvalidValue;  // (act1_shape refuses it)
+}
+template <class GO>
+int a1_generic_ln(const A1Shape &a, GO &go1) {
+  if (a.h == 128) {
+    if (a.nl == 2) return a1_generic_ln_f0<2, 128>(a.f0, go1);
+    if (a.nl == 3) return a1_generic_ln_f0<3, 128>(a.f0, go1);
+    return a1_generic_ln_f0<4, 128>(a.f0, go1);
+  }
+  if (a.nl == 2) return a1_generic_ln_f0<2, 64>(a.f0, go1);
+  if (a.nl == 3) return a1_generic_ln_f0<3, 64>(a.f0, go1);
+  return a1_generic_ln_f0<4, 64>(a.f0, go1);
+}
 // ... and of the controller form (the assembly applies the prologue: PRO false; D = 1)
 template <int NL, int H, class GO>
 int a1_generic_ctl_f0(int f0, GO &go1) {
@@ -1562,6 +1658,9 @@ A1Shape act1_shape(const DevProgram &p) {
   if (f0 > 4 || p.lds_stride < std::max(64 * f0, H)) return a;
   // weights per lane beyond the registers of 3 waves per SIMD (168): the r04 form
   if (H == 128 && p.nl == 4 && f0 == 4) return a;
+  // ... and, for a LayerNormalization program, of 128^2 with four layer-0 float4s per lane
+  // (the LN pass's registers): the multi-workgroup form
+  if (program_has_ln(p) && H == 128 && p.nl == 3 && f0 == 4) return a;
   a.nl = p.nl;
   a.h = H;
   a.f0 = f0;
@@ -1578,6 +1677,9 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
                      unsigned long long *actg, unsigned *err, unsigned *done, unsigned long long idle_ticks,
                      const unsigned *yield, const DevCtl *ctl, void *stream) {
   if (!resident1_fits(p, ctl != nullptr)) return (int)hipErrorInvalidValue;
+  // a LayerNormalization program: policy_act1_kernel's act() form only (LN = true)
+  const bool ln = program_has_ln(p);
+  if (ln && (ctl || !resident1_ctl_granules(p))) return (int)hipErrorInvalidValue;
   const size_t lds = resident1_lds_bytes(p, ctl != nullptr);  // (r04's forms)
   auto go = [&](auto kern, int nt) {
     if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
@@ -1605,6 +1707,11 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
                                          (ctl ? (size_t)ctl_lds_floats(GO2PI_SMALL_MAXB, p.in_dim) +
                                                     (size_t)a1.f0 * (a1.h / 32) * 512 * 4 + (size_t)(a1.h / 64) * 256 * 4 +
                                                     (size_t)GO2PI_SMALL_MAXB * p.in_dim
+                                              : 0) +
+                                         // (an LN program of four 128-wide layers: layer 0's and the
+                                         // head's weights in LDS, as the controller form keeps them)
+                                         ((!ctl && ln && a1.h == 128 && a1.nl == 4)
+                                              ? (size_t)a1.f0 * (a1.h / 32) * 512 * 4 + (size_t)(a1.h / 64) * 256 * 4
                                               : 0));
     auto go1 = [&](auto kern, int cw) {
       if (lds1 > 64 * 1024) {
@@ -1623,6 +1730,7 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
     const bool pro = p.pre_sub || p.pre_div || p.pre_mul || p.pre_clip;
     const char *cv = std::getenv("GO2PI_A1_CW");
     const int cw = cv && std::atoi(cv) == 4 ? 4 : 8;
+    if (ln) return a1_generic_ln(a1, go1);
     if (ctl) {  // the controller form: one sweep in flight (three loads per lane), eight compute waves
       if (a1.nl == 4 && a1.h == 128 && a1.f0 == 2 && elu1)
         return go1(policy_act1_kernel<4, 128, 2, 0x0111u, 1, false, 8, true>, 8);
@@ -1695,6 +1803,16 @@ int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned
                        actg, gran, gstride, mirror, err, done, idle_ticks, ctl ? *ctl : DevCtl{}, hgran, hidden, yield);
     return (int)hipGetLastError();
   };
+  // the general instantiations: an LN program, or layer inputs past one sweep round
+  // (engine.cpp selects neither the controller nor the recurrent form for those)
+  const bool gen = program_small_general(p);
+  if (gen && (ctl || rnn)) return (int)hipErrorInvalidValue;
+  if (gen) {
+    if (local0 && nf == 8) return go(policy_resident_kernel<8, false, 0, true>);
+    if (local0 && nf == 12) return go(policy_resident_kernel<12, false, 0, true>);
+    if (local0 && nf == 16) return go(policy_resident_kernel<16, false, 0, true>);
+    return go(policy_resident_kernel<0, false, 0, true>);
+  }
   if (lstm) return go(policy_resident_kernel<0, false, 2>);
   if (rnn) return go(policy_resident_kernel<0, false, 1>);
   if (ctl) {

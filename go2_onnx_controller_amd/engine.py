@@ -22,7 +22,7 @@ EXPORTS = [
     "go2pi_io_name", "go2pi_io_shape", "go2pi_io_dims", "go2pi_run", "go2pi_run_device",
     "go2pi_run_sequence_device", "go2pi_reset_hidden", "go2pi_get_hidden", "go2pi_set_hidden",
     "go2pi_hidden_dim", "go2pi_sync", "go2pi_get_cost", "go2pi_batched_kernel", "go2pi_inspect_model",
-    "go2pi_diag_stamps", "go2pi_resident_kernel", "go2pi_resident_launches",
+    "go2pi_diag_stamps", "go2pi_resident_kernel", "go2pi_resident_launches", "go2pi_small_kernel",
     "go2pi_last_error", "go2pi_version", "go2pi_ctl_default_params", "go2pi_ctl_set_params",
     "go2pi_ctl_history", "go2pi_controller_step", "go2pi_controller_step_device",
 ]
@@ -58,6 +58,7 @@ class Opts(ctypes.Structure):
         ("action_clip", ctypes.c_float),
         ("action_scale", ctypes.c_float),
         ("resident_ms", ctypes.c_int32),
+        ("ln_small", ctypes.c_int32),
     ]
 
 
@@ -124,6 +125,7 @@ def lib():
             "go2pi_batched_kernel": (ctypes.c_int, [P, ctypes.c_char_p, ctypes.c_size_t]),
             "go2pi_resident_kernel": (ctypes.c_int, [P, ctypes.c_char_p, ctypes.c_size_t]),
             "go2pi_resident_launches": (ctypes.c_int, [P, P]),
+            "go2pi_small_kernel": (ctypes.c_int, [P, ctypes.c_char_p, ctypes.c_size_t]),
             "go2pi_diag_stamps": (ctypes.c_int, [P, P, I64]),
             "go2pi_inspect_model": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]),
             "go2pi_last_error": (ctypes.c_char_p, []),
@@ -135,8 +137,8 @@ def lib():
             "go2pi_controller_step_device": (ctypes.c_int, [P, P, P, P, P, P, P, P, P, I64, P]),
         }
         for name, (res, args) in sig.items():
-            if name in ("go2pi_batched_kernel", "go2pi_resident_kernel", "go2pi_resident_launches") and not hasattr(L, name) and \
-                    os.environ.get("GO2PI_LIB"):
+            if name in ("go2pi_batched_kernel", "go2pi_resident_kernel", "go2pi_resident_launches",
+                        "go2pi_small_kernel") and not hasattr(L, name) and os.environ.get("GO2PI_LIB"):
                 continue  # an older diagnostics build (A/B tooling): the name query is optional there
             fn = getattr(L, name)
             fn.restype = res
@@ -162,7 +164,7 @@ class Engine:
 
     def __init__(self, model, device=0, max_batch=4096, use_graph=True, waves=0, small_batch=0,
                  obs_mean=None, obs_std=None, obs_clip=0.0, action_tanh=False, action_clip=0.0,
-                 action_scale=0.0, log_level=2, resident_ms=0):
+                 action_scale=0.0, log_level=2, resident_ms=0, ln_small=False):
         L = lib()
         o = Opts()
         L.go2pi_default_opts(ctypes.byref(o))
@@ -180,6 +182,9 @@ class Engine:
         o.obs_clip, o.action_tanh = float(obs_clip), int(bool(action_tanh))
         o.action_clip, o.action_scale = float(action_clip), float(action_scale)
         o.resident_ms = int(resident_ms)  # > 0: batch <= 8 run() served by a resident kernel
+        # a LayerNormalization policy at batch <= 8: the single-launch kernel and, with
+        # resident_ms > 0, a resident kernel (False: one launch per layer)
+        o.ln_small = int(bool(ln_small))
         h = ctypes.c_void_p()
         if isinstance(model, (bytes, bytearray)):
             buf = bytes(model)
@@ -215,6 +220,12 @@ class Engine:
             kb = ctypes.create_string_buffer(128)
             _check(L.go2pi_resident_kernel(h, kb, 128))
             self.resident_kernel = kb.value.decode()  # e.g. "policy_wide_kernel<4, 8, 12, 0> ring=vram"
+        # what serves a host run() at batch <= 8 when no resident kernel does
+        self.small_kernel = "unknown"
+        if hasattr(L, "go2pi_small_kernel") and L.go2pi_small_kernel.argtypes:
+            kb = ctypes.create_string_buffer(128)
+            _check(L.go2pi_small_kernel(h, kb, 128))
+            self.small_kernel = kb.value.decode()  # e.g. "policy_latency_kernel", "gemv_layer_kernel graph"
 
     @property
     def resident_launches(self):

@@ -69,6 +69,12 @@ typedef struct go2pi_opts {
      final layer is <= 16 wide; others keep the launch path. 0 (default): one launch
      per call. Any other call on the engine first stops the resident kernel. */
   int32_t resident_ms;
+  /* 1: a LayerNormalization policy at batch <= 8 is served like an LN-free one: by the
+     single-launch kernel and, with resident_ms > 0, by a resident kernel (go2pi_create).
+     0 (default): one launch per layer, as before this field existed. No effect on a
+     policy without LayerNormalization, on a recurrent one, or above batch 8. (The field
+     fills what was tail padding: a zero-initialised struct of the earlier layout reads 0.) */
+  int32_t ln_small;
 } go2pi_opts;
 
 void go2pi_default_opts(go2pi_opts *opts);
@@ -83,8 +89,13 @@ void go2pi_default_opts(go2pi_opts *opts);
    a layer, with a Mul / Div / Add between it and its activation), another axis or
    stash_type, a Scale / B of another length or not constant, and a consumed Mean /
    InvStdDev output fail with GO2PI_E_MODEL and a message of their own. Such a policy is
-   served by the general batched kernel and, at batch <= 8, by one launch per layer; the
-   lean, single-launch and resident (resident_ms) forms do not serve it yet. */
+   served by the general batched kernel and, at batch <= 8, by one launch per layer. With
+   opts.ln_small = 1 a dense one is served at batch <= 8 by the single-launch kernel, and
+   with resident_ms > 0 by a resident kernel: policy_act1_kernel where its shape applies
+   (hidden layers 64 or 128 wide), else the multi-workgroup policy_resident_kernel (never
+   policy_wide_kernel or policy_resident1_kernel). Its controller tick at batch <= 8 is the
+   single launch (no resident controller form), and a recurrent LN policy keeps the
+   general body. The lean / pipeline batched kernels do not serve LN. */
 int go2pi_create(const char *onnx_path, const go2pi_opts *opts, go2pi_engine **out);
 int go2pi_create_from_memory(const void *onnx_bytes, size_t nbytes, const go2pi_opts *opts,
                              go2pi_engine **out);
@@ -150,6 +161,15 @@ int go2pi_batched_kernel(const go2pi_engine *e, char *buf, size_t cap);
    "policy_wide_kernel<4, 8, 12, 0> ring=vram". For tests and profiling tools; no
    compute. */
 int go2pi_resident_kernel(const go2pi_engine *e, char *buf, size_t cap);
+
+/* Name of what serves a host go2pi_run at batch <= 8 on this engine when no resident
+   kernel does, following go2pi_run's selection: "policy_latency_kernel" (one launch for
+   the whole policy; a LayerNormalization program's instantiation of it is the symbol
+   policy_latency_ln_kernel), "gemv_layer_kernel graph" (one launch per layer replayed as a
+   hipGraph; "gemv_layer_kernel" with use_graph = 0), or the batched kernel's name
+   (go2pi_batched_kernel) when small_batch = -1 or the policy is recurrent. For tests and
+   profiling tools; no compute. */
+int go2pi_small_kernel(const go2pi_engine *e, char *buf, size_t cap);
 
 /* Resident kernel launches this engine has made so far (one serves every request
    until it idles out or another call stops it; a kernel that aborts on a request
