@@ -1782,7 +1782,10 @@ int go2pi_batched_kernel(const go2pi_engine *e, char *buf, size_t cap) {
                     h, e->prog.gru.H / 64);
     else if (t && e->prog.w4_plain)  // the lean pipeline kernel: <tiles per wave, head tiles, layer-0 chunks mod 4,
                                      // act, hidden layers, waves per workgroup (4)>
-      std::snprintf(buf, cap, "policy_mlp_kernel<%d, %d, %d, %d, %d, 4>", t, h, c0m, e->prog.w4_actc, e->prog.w4_nhc);
+      // (what a one-tick launch runs: the one-tick form, or the looped one for a head with an activation)
+      std::snprintf(buf, cap, "%s<%d, %d, %d, %d, %d, 4>",
+                    e->prog.head_act == 0 ? "policy_mlp_kernel" : "policy_mlp_seq_kernel", t, h, c0m, e->prog.w4_actc,
+                    e->prog.w4_nhc);
     else
       std::snprintf(buf, cap, "policy_fused_kernel<%d, %d, %d, %d, %d, %d, %d>", e->waves, t, h, c0m,
                     (e->prog.has_gru && e->prog.gru.cell == 1) ? 1 : 0, t ? e->prog.w4_actc : -1,

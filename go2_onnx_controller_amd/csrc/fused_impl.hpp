@@ -1251,7 +1251,11 @@ __device__ __forceinline__ void w4_prefill(const float *l0w, float4 (&f)[4][TPW]
 // a 48- or 98-wide observation padded to 16 rather than 64): layer 0 starts on
 // ring slot (4 - C0M) & 3 so that its last chunk uses slot 3 and layer 1 starts on
 // slot 0 as always.
-template <int TPW, int HT, bool CTL, bool PL, int C0M, int ACTC = -1, int NHC = 0, int NW = 4>
+// T1: the one-tick lean form (w4_tick_body: step 0 only, `pre` set, the head without
+// an activation). Its caller issued the ring's loads FIRST and the staging loads
+// after them, so the barrier below waits for every load; the head's tail is the
+// partial sums, the bias and the store.
+template <int TPW, int HT, bool CTL, bool PL, int C0M, int ACTC = -1, int NHC = 0, int NW = 4, bool T1 = false>
 __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, float *X0, float *Y0, int S,
                                         f32x4 *scratch, int *flags, float *lbias, int &ep, int wave, int lane,
                                         float *ac, const CtlView cv, int row0, int B, const DevCtl &ctl,
@@ -1345,7 +1349,9 @@ __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, 
   // the compiler may sink them below this barrier: with run-time branches after it (an
   // r05 issue-priority experiment) it did, vmcnt(RD * TPW) waited for nothing, and rows
   // staged by waves 4-7 were read before they landed.)
-  if (!ctl_here) wg_barrier_vm<NW == 8 ? 0 : RD * TPW>();
+  // (T1: the ring's loads are the oldest, the staging loads follow them: vmcnt(0))
+  static_assert(!T1 || (PL && !CTL), "the one-tick form is the lean kernel's");
+  if (!ctl_here) wg_barrier_vm<(NW == 8 || T1) ? 0 : RD * TPW>();
   GO2PI_STAMP(P, threadIdx.x == 0 && step == 0, 4);
   if constexpr (CTL) {
     if (ctl.status && (int)threadIdx.x < min(GO2PI_TILE_ROWS, B - row0)) ctl.status[row0 + threadIdx.x] = CL.nanf[threadIdx.x];
@@ -1517,11 +1523,15 @@ __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, 
       // to the store, profiles/r05_clock_mlp512.json tail_store.)
       const int row = row0 + (lane & 15), n0 = wave * 16 + ((lane >> 4) << 2);
       float4 v = make_float4(hs[0][0] + hbv[0].x, hs[0][1] + hbv[0].y, hs[0][2] + hbv[0].z, hs[0][3] + hbv[0].w);
-      if (hot.head_act != 0) {
-        v.x = act_fn(hot.head_act, hot.head_alpha, hot.head_beta, v.x);
-        v.y = act_fn(hot.head_act, hot.head_alpha, hot.head_beta, v.y);
-        v.z = act_fn(hot.head_act, hot.head_alpha, hot.head_beta, v.z);
-        v.w = act_fn(hot.head_act, hot.head_alpha, hot.head_beta, v.w);
+      // (T1: the engine launches the one-tick form only for an identity head; the
+      // run-time test alone left the whole activation ladder in the tail's code)
+      if constexpr (!T1) {
+        if (hot.head_act != 0) {
+          v.x = act_fn(hot.head_act, hot.head_alpha, hot.head_beta, v.x);
+          v.y = act_fn(hot.head_act, hot.head_alpha, hot.head_beta, v.y);
+          v.z = act_fn(hot.head_act, hot.head_alpha, hot.head_beta, v.z);
+          v.w = act_fn(hot.head_act, hot.head_alpha, hot.head_beta, v.w);
+        }
       }
       if (row < B) {  // (ac = the action rows of all steps, this step's at step * B rows)
         float *o = ac + ((size_t)step * B + row) * hot.head_n;
@@ -1639,6 +1649,80 @@ __device__ __forceinline__ void w4_plain_body(const DevProgram &P, const float *
     w4_step<TPW, HT, false, true, C0M, ACTC, NHC, NW>(P, hot, bufA, bufB, S, scratch, flags, lbias, ep, wave, lane, act, CtlView{}, row0, B, DevCtl{},
                                        CtlLds{}, step, ring_none, false);
   }
+  GO2PI_STAMP(P, tid == 0, 2);
+  GO2PI_STAMP_RT(P, tid == 0, 3);
+}
+
+// The one-tick form of the lean pipeline kernel (policy_mlp_kernel; the looped body
+// above is policy_mlp_seq_kernel's): what every batched launch but a device-side
+// sequence runs. No step loop, so none of its preheader (every layer's chunk
+// offsets, row clamps and bias addresses hoisted in front of the first load, the
+// SGPRs among them spilled to VGPR lanes), and the prologue's loads go out in the
+// order of their cost: the ring's fragments first (the only prologue loads every
+// workgroup of an XCD shares, and the long pole of a cold launch; they need the wave
+// id, the lane and the preloaded l0w), then the observation rows, then the biases.
+// dims bit 31: the host's "grid > GO2PI_YIELD_MIN_GRID" (no read of the hidden grid
+// size in front of block 0's first load); the yield bump follows the loads.
+// The head has no activation (the engine launches the looped kernel otherwise).
+template <int TPW, int HT, int C0M, int ACTC, int NHC, int NW = 4>
+__device__ __forceinline__ void w4_tick_body(const DevProgram &P, const float *__restrict__ obs,
+                                             float *__restrict__ act, const float *l0w, const float *bpack, int B,
+                                             unsigned dims, unsigned *yield) {
+  GO2PI_ENTRY_CLOCK();
+  extern __shared__ float4 lds4[];
+  float *lds = reinterpret_cast<float *>(lds4);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  float4 ring[4][TPW];
+  w4_prefill<TPW, C0M, NW>(l0w, ring, wave, lane);
+  asm volatile("" ::: "memory");  // the ring's loads stay ahead of the staging loads
+  const int in_dim = (int)(dims & 0xFFFu), c0 = (int)((dims >> 12) & 0xFFu), nh = (int)((dims >> 20) & 0xFFu);
+  const int nbias = (NHC > 0 ? NHC : nh) * 16 * NW * TPW;
+  const W4Hot hot = W4Hot{l0w, nullptr, nullptr, bpack, nullptr, nbias, 0, c0, 0, 0, 0.f, 0.f, 1, 0.f, 0.f};
+  constexpr int S = 16 * NW * TPW + 4;  // = P.lds_stride (the engine selects this kernel only then)
+  float *bufA = lds, *bufB = lds + GO2PI_TILE_ROWS * S;
+  f32x4 *scratch = reinterpret_cast<f32x4 *>(lds + 2 * GO2PI_TILE_ROWS * S);
+  int *flags = reinterpret_cast<int *>(lds + 2 * GO2PI_TILE_ROWS * S + 256 * NW * HT);
+  float *lbias = reinterpret_cast<float *>(flags) + GO2PI_FLAG_FLOATS;
+  const int row0 = blockIdx.x * GO2PI_TILE_ROWS;
+  const int nch = (16 * c0 + 63) >> 6;  // 64-column chunks of the observation tile
+  // wave w stages rows w, w + NW, ... in whole 64-column chunks by direct-to-LDS loads
+  // (chunk-outer: one pass of straight-line code for an observation of up to 64 columns)
+  for (int c = 0; c < nch; ++c) {
+    const int col = min(c * 64 + lane, in_dim - 1);
+#pragma unroll
+    for (int i = 0; i < GO2PI_TILE_ROWS / NW; ++i) {
+      const int r = wave + NW * i, row = min(row0 + r, B - 1);
+      __builtin_amdgcn_global_load_lds((gvoid_t *)(obs + (size_t)row * in_dim + col),
+                                       (lvoid_t *)(bufA + r * S + c * 64), 4, 0, 0);
+    }
+  }
+  if constexpr (NHC > 0) {
+    // a compile-time bias count (a multiple of 64): glds_copy's passes unrolled, no clamp
+    // (its loop took 11 instructions per load; this takes 5 to 6)
+    constexpr int NB = NHC * 16 * NW * TPW, FULL = NB / (NW * 64);
+#pragma unroll
+    for (int k = 0; k < FULL; ++k)
+      __builtin_amdgcn_global_load_lds((gvoid_t *)(bpack + (k * NW + wave) * 64 + lane),
+                                       (lvoid_t *)(lbias + (k * NW + wave) * 64), 4, 0, 0);
+    if constexpr (NB % (NW * 64) != 0) {
+      if ((FULL * NW + wave) * 64 < NB)
+        __builtin_amdgcn_global_load_lds((gvoid_t *)(bpack + (FULL * NW + wave) * 64 + lane),
+                                         (lvoid_t *)(lbias + (FULL * NW + wave) * 64), 4, 0, 0);
+    }
+  } else {
+    glds_copy(lbias, bpack, nbias, wave, lane, NW);
+  }
+  if (tid < NW) flags[tid] = 0;
+  // tell idle resident kernels on this device to give their CUs back (resident.hip)
+  if (blockIdx.x == 0 && tid == 0 && (dims >> 31))
+    __hip_atomic_fetch_add(yield, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  GO2PI_STAMP_ENTRY(P, tid == 0);
+  GO2PI_STAMP(P, tid == 0, 40);
+  GO2PI_STAMP(P, tid == 0, 41);
+  int ep = 0;  // flag epochs published so far (the same in every wave)
+  w4_step<TPW, HT, false, true, C0M, ACTC, NHC, NW, true>(P, hot, bufA, bufB, S, scratch, flags, lbias, ep, wave, lane,
+                                                          act, CtlView{}, row0, B, DevCtl{}, CtlLds{}, 0, ring, true);
   GO2PI_STAMP(P, tid == 0, 2);
   GO2PI_STAMP_RT(P, tid == 0, 3);
 }
@@ -2157,7 +2241,9 @@ __global__ __launch_bounds__(NW * 64) void policy_fused_kernel(const DevProgram 
   fused_body<NW, false, W4T, W4H, C0M, RNN, ACTC, NHC>(*Pd, obs, act, hidden, B, steps, DevCtl{});
 }
 
-// The lean pipeline kernel (w4_plain_body). Argument order = preload order: the
+// The lean pipeline kernel, one tick (w4_tick_body; r07: mlp512 34.86 -> 34.20 us,
+// shipped 5.75 -> 5.2 us against the looped body run for one step, DESIGN §4.1,
+// profiles/r07_ab_lean_tick.json). Argument order = preload order: the
 // first 16 dwords of the kernel arguments arrive in SGPRs (kernels_w4_t*.hip are
 // built with -amdgpu-kernarg-preload-count=16); these are 13.
 // NW: waves per workgroup, 4 (one per SIMD, the r01-r04 pipeline) or 8 (two per SIMD,
@@ -2170,6 +2256,19 @@ __global__ __launch_bounds__(NW * 64) void policy_mlp_kernel(const float *__rest
                                                              const float *__restrict__ bpack,
                                                              const DevProgram *__restrict__ Pd, int B, int steps,
                                                              unsigned dims, unsigned *yield) {
+  (void)steps;  // one tick (w4_tick_body); the same arguments as the looped kernel below
+  w4_tick_body<TPW, HT, C0M, ACTC, NHC, NW>(*Pd, obs, act, l0w, bpack, B, dims, yield);
+}
+
+// The looped form (w4_plain_body): `steps` ticks in one launch (a device-side
+// sequence), and the one-tick launch of a policy whose head has an activation.
+template <int TPW, int HT, int C0M, int ACTC, int NHC, int NW = 4>
+__global__ __launch_bounds__(NW * 64) void policy_mlp_seq_kernel(const float *__restrict__ obs,
+                                                                 float *__restrict__ act,
+                                                                 const float *__restrict__ l0w,
+                                                                 const float *__restrict__ bpack,
+                                                                 const DevProgram *__restrict__ Pd, int B, int steps,
+                                                                 unsigned dims, unsigned *yield) {
   w4_plain_body<TPW, HT, C0M, ACTC, NHC, NW>(*Pd, obs, act, l0w, bpack, B, steps, dims, yield);
 }
 

@@ -66,6 +66,11 @@ int w4_configure<TPW>(const DevProgram &p) {
     hipError_t e = hipFuncSetAttribute(batched_kernel<HT, PL, C0M, RNN, ACTC, NHC>(), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)fused_lds_bytes(p, 4));
     if (e != hipSuccess) return (int)e;
+    if constexpr (PL) {  // the lean kernel's looped form (w4_launch)
+      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_mlp_seq_kernel<TPW, HT, C0M, ACTC, NHC>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds_bytes(p, 4));
+      if (e != hipSuccess) return (int)e;
+    }
     if constexpr (!PL && C0M == 0 && ACTC == 1 && NHC == 3) {  // (RNN: the GRU or the LSTM tick)
       if (const void *k = gru_lean_kernel<HT>(p)) {
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds_bytes(p, 4));
@@ -91,10 +96,20 @@ int w4_launch<TPW>(const DevProgram &p, const DevProgram *p_dev, const float *ob
   const size_t lds = fused_lds_bytes(p, 4);
   return with_shape(p, [&]<int HT, bool PL, int C0M, int RNN, int ACTC, int NHC>(Shape<HT, PL, C0M, RNN, ACTC, NHC>) {
     if constexpr (PL) {
-      const unsigned dims = (unsigned)p.in_dim | (unsigned)p.c0 << 12 | (unsigned)(p.nl - 1) << 20;
-      hipLaunchKernelGGL((policy_mlp_kernel<TPW, HT, C0M, ACTC, NHC>), grid, dim3(256), lds,
-                         reinterpret_cast<hipStream_t>(stream), obs, act, p.l0_w, p.bpack, p_dev, batch, steps, dims,
-                         p.yield);
+      // dims bit 31: the launch bumps the yield counter (the one-tick form reads it here
+      // instead of the grid size)
+      const unsigned dims = (unsigned)p.in_dim | (unsigned)p.c0 << 12 | (unsigned)(p.nl - 1) << 20 |
+                            (grid.x > GO2PI_YIELD_MIN_GRID ? 1u << 31 : 0u);
+      // one tick of a policy with an identity head (every exported one): the one-tick
+      // form; a device-side sequence or a head with an activation: the looped form
+      if (steps == 1 && p.head_act == 0)
+        hipLaunchKernelGGL((policy_mlp_kernel<TPW, HT, C0M, ACTC, NHC>), grid, dim3(256), lds,
+                           reinterpret_cast<hipStream_t>(stream), obs, act, p.l0_w, p.bpack, p_dev, batch, steps, dims,
+                           p.yield);
+      else
+        hipLaunchKernelGGL((policy_mlp_seq_kernel<TPW, HT, C0M, ACTC, NHC>), grid, dim3(256), lds,
+                           reinterpret_cast<hipStream_t>(stream), obs, act, p.l0_w, p.bpack, p_dev, batch, steps, dims,
+                           p.yield);
     } else {
       if constexpr (C0M == 0 && ACTC == 1 && NHC == 3) {
         if (const void *k = gru_lean_kernel<HT>(p); k && batch < (1 << 20)) {  // the lean GRU / LSTM tick (w4_gru_body)
