@@ -18,6 +18,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <limits>
@@ -35,10 +36,62 @@
 #include "onnx_model.hpp"
 #include "program.hpp"
 
-static bool gru_lean_on();
 namespace {
 
+using go2pi::ResForm;
+
 thread_local std::string g_last_error;
+
+// The process's diagnostic switches (GO2PI_* environment variables; DESIGN §4.5 lists
+// them), read once per engine at the top of build(): every choice an engine makes from
+// them is made there and holds for its life. Except where noted a switch is on when the
+// variable is set, to any value.
+struct Switches {
+  bool req_host;               // REQ_HOST: the request ring in pinned host memory (bar_take)
+  bool no_head_fuse, no_w4;    // NO_HEAD_FUSE: no head fusion, and so no 4-wave pipeline; NO_W4: no pipeline
+  bool k0_pad64;               // K0_PAD64: the pipeline's layer 0 padded to 64 columns, not 16
+  bool small_chain;            // SMALL_CHAIN: batch <= 8 by the GEMV chain (no single launch, no resident form)
+  unsigned epoch0;             // EPOCH0=<u32>: the first granule tag instead of 1; 0 (unset, out of range): ignored
+  bool diag_stamps;            // DIAG_STAMPS: per-workgroup clock stamps
+  bool no_plain;               // NO_PLAIN: the general pipeline body, not the lean kernel
+  bool lean_rt_act, lean_rt_nh;  // LEAN_RT_ACT / _NH: the lean kernel's activation / layer count read at run time
+  // GRU_GENERAL: the general body, not the lean recurrent tick (r05 same-box A/B, GRU-256 at
+  // 4096 robots: 56.7 against 60.5-60.9 us per one-tick launch); CTL_GENERAL: ... not the lean controller tick
+  bool gru_general, ctl_general;
+  bool res_multi;              // RES_MULTI: the multi-workgroup resident kernel for every form
+  bool res_r1w;                // RES_R1W: never policy_act1_kernel (r04's policy_resident1_kernel where it fits)
+  bool res_tiled0;             // RES_TILED0: the multi-workgroup kernel's layer 0 tiled, not local
+  int a1_depth, a1_cw;         // A1_DEPTH: policy_act1_kernel's poll sweeps in flight, 1 for the value 1, else 2;
+                               // A1_CW: its compute waves, 4 for the value 4, else 8
+
+  static Switches read() {
+    auto env = [](const char *name) { return std::getenv(name); };  // (the engine's only look at the environment)
+    auto on = [&](const char *name) { return env(name) != nullptr; };
+    auto num = [&](const char *name) { return env(name) ? std::atoi(env(name)) : 0; };
+    const unsigned long long e0 = env("GO2PI_EPOCH0") ? std::strtoull(env("GO2PI_EPOCH0"), nullptr, 0) : 0ull;
+    return Switches{.req_host = on("GO2PI_REQ_HOST"), .no_head_fuse = on("GO2PI_NO_HEAD_FUSE"),
+                    .no_w4 = on("GO2PI_NO_W4"), .k0_pad64 = on("GO2PI_K0_PAD64"),
+                    .small_chain = on("GO2PI_SMALL_CHAIN"), .epoch0 = e0 <= 0xFFFFFFFFull ? (unsigned)e0 : 0u,
+                    .diag_stamps = on("GO2PI_DIAG_STAMPS"), .no_plain = on("GO2PI_NO_PLAIN"),
+                    .lean_rt_act = on("GO2PI_LEAN_RT_ACT"), .lean_rt_nh = on("GO2PI_LEAN_RT_NH"),
+                    .gru_general = on("GO2PI_GRU_GENERAL"), .ctl_general = on("GO2PI_CTL_GENERAL"),
+                    .res_multi = on("GO2PI_RES_MULTI"), .res_r1w = on("GO2PI_RES_R1W"),
+                    .res_tiled0 = on("GO2PI_RES_TILED0"), .a1_depth = num("GO2PI_A1_DEPTH") == 1 ? 1 : 2,
+                    .a1_cw = num("GO2PI_A1_CW") == 4 ? 4 : 8};
+  }
+};
+
+// Spin with the host's pause cadence until done() holds; the clock is read every 1024
+// turns and the wait gives up after 2 s. Returns done()'s last word.
+template <class F>
+bool spin_until(F &&done) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (unsigned it = 0; !done(); ++it) {
+    __builtin_ia32_pause();
+    if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) return done();
+  }
+  return true;
+}
 
 struct HipError : std::runtime_error {
   int code;
@@ -131,10 +184,11 @@ bool host_mapped(const void *p, size_t bytes) {
 }
 
 // a host-writable device block of at least `bytes` (out: its size) on the current
-// device `device`, zeroed; nullptr when the host cannot map this device's memory
-void *bar_take(int device, size_t &bytes) {
+// device `device`, zeroed; nullptr when the host cannot map this device's memory, or
+// with req_host (Switches: no block wanted)
+void *bar_take(int device, size_t &bytes, bool req_host) {
   bytes = (bytes + 4095) & ~(size_t)4095;
-  if (std::getenv("GO2PI_REQ_HOST")) return nullptr;
+  if (req_host) return nullptr;
   void *p = nullptr;
   {
     std::lock_guard<std::mutex> lk(g_pin_mu);
@@ -198,6 +252,7 @@ std::mutex g_res_mu;
 struct go2pi_engine {
   go2pi::Model model;
   go2pi_opts opts{};
+  Switches sw{};  // as the environment stood when build() began
   int device = 0;
   int waves = 8;
   int small_batch = 8;
@@ -231,14 +286,13 @@ struct go2pi_engine {
   // resident batch <= SMALL_MAXB path (resident.hip, opts.resident_ms > 0)
   bool resident_ok = false, resident_live = false;
   std::atomic<int> res_flag{0};  // resident_live, readable from other threads (evict_residents)
-  bool resident_ctl_ok = false;  // the controller-tick form applies (dense policies)
+  // the kernel that serves act() and the one that serves a controller tick (program.hpp
+  // ResForm), decided in build(); res_ctl None: ticks are served by a launch each (the
+  // controller form applies to dense policies without LayerNormalization)
+  ResForm res_act = ResForm::None, res_ctl = ResForm::None;
   unsigned long long *d_hgran = nullptr;  // GRU form: [2][SMALL_MAXB][H] hidden-row granules (two buffers)
   bool resident_ctl = false;  // the live kernel is the controller-tick form
-  bool resident1 = false;     // act() form in one workgroup (resident.hip policy_resident1_kernel)
-  bool resident1_ctl = false; // controller form in one workgroup (512 threads)
-  bool wide = false;          // act() form for wide policies (resident_wide.hip policy_wide_kernel, r06)
   int64_t res_launches = 0;   // resident kernel launches (go2pi_resident_launches)
-  bool ctl_gran_ok = false;   // ... answered in granules (policy_act1_kernel, r05): no done word per tick
   std::vector<float> res_rows = std::vector<float>(GO2PI_SMALL_MAXB * (GO2PI_CTL_RAW + 16 * GO2PI_CTL_STEP_DIM));
   unsigned long long *h_req = nullptr, *m_req = nullptr;  // request granules: host view, device view
   size_t req_bar_bytes = 0;  // > 0: the ring is in device memory the host writes through the BAR (bar_take)
@@ -330,12 +384,8 @@ struct go2pi_engine {
   // false: not observed within 2 s (the caller falls back to a stream sync).
   bool spin_done() {
     const unsigned want = last_epoch;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned it = 0; __atomic_load_n(h_done, __ATOMIC_ACQUIRE) != want; ++it) {
-      __builtin_ia32_pause();
-      if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-    }
-    return __atomic_load_n(h_done, __ATOMIC_ACQUIRE) == want;
+    const unsigned *done = h_done;
+    return spin_until([=] { return __atomic_load_n(done, __ATOMIC_ACQUIRE) == want; });
   }
 
   // ---- resident path: one launch serves every batch <= SMALL_MAXB go2pi_run
@@ -362,18 +412,26 @@ struct go2pi_engine {
     __atomic_store_n(h_req, 0ull, __ATOMIC_SEQ_CST);
     __atomic_store_n(h_done, 0u, __ATOMIC_SEQ_CST);
     std::memset(h_actg, 0, sizeof(unsigned long long) * n_actg);
-    if (ctl ? resident1_ctl : resident1)
-      hip_check(go2pi::launch_resident1(prog, d_prog, m_req, m_actg, m_err, m_done, res_idle_ticks, prog.yield, ctl,
-                                        stream),
-                "resident launch (one workgroup)");
-    else if (!ctl && wide)
-      hip_check(go2pi::launch_resident_wide(prog, d_prog, m_req, m_actg, d_gran, gstride, m_err, m_done, res_idle_ticks,
-                                            prog.yield, stream),
-                "resident launch (wide policy)");
-    else
-      hip_check(go2pi::launch_resident(prog, d_prog, m_req, m_actg, d_gran, gstride, d_mirror, m_err, m_done,
-                                       res_idle_ticks, ctl, d_hgran, d_hidden, prog.yield, stream),
-                "resident launch");
+    const ResForm form = ctl ? res_ctl : res_act;
+    switch (form) {
+      case ResForm::Act1:
+      case ResForm::R1:
+        hip_check(go2pi::launch_resident1(prog, d_prog, m_req, m_actg, m_err, m_done, res_idle_ticks, prog.yield, ctl,
+                                          form, sw.a1_depth, sw.a1_cw, stream),
+                  "resident launch (one workgroup)");
+        break;
+      case ResForm::Wide:
+        hip_check(go2pi::launch_resident_wide(prog, d_prog, m_req, m_actg, d_gran, gstride, m_err, m_done,
+                                              res_idle_ticks, prog.yield, stream),
+                  "resident launch (wide policy)");
+        break;
+      case ResForm::Multi:
+        hip_check(go2pi::launch_resident(prog, d_prog, m_req, m_actg, d_gran, gstride, d_mirror, m_err, m_done,
+                                         res_idle_ticks, ctl, d_hgran, d_hidden, prog.yield, sw.res_tiled0, stream),
+                  "resident launch");
+        break;
+      case ResForm::None: throw ApiError("no resident kernel serves this request", GO2PI_E_INVALID);
+    }
     ++res_launches;
     resident_live = true;
     res_flag.store(1);
@@ -454,7 +512,7 @@ struct go2pi_engine {
       std::memcpy(h_act + j, &bits, 4);
     }
   }
-  // the controller form's answer granules to the caller's buffers (ctl_gran_ok)
+  // the controller form's answer granules to the caller's buffers (res_ctl Act1)
   void ctl_take(int64_t batch, float *obs, float *action, double *q_des, double *kp, double *kd,
                 uint32_t *status) const {
     const go2pi::CtlGran G = go2pi::ctl_gran(model.in_dim);
@@ -515,53 +573,50 @@ struct go2pi_engine {
       }
       __atomic_store_n(h_req, ((unsigned long long)e0 << 32) | (unsigned)batch | flags, __ATOMIC_RELEASE);
       if (req_bar_bytes) _mm_sfence();  // the BAR mapping is write-combined: send the request now
-      const auto t0 = std::chrono::steady_clock::now();
-      unsigned d;
+      unsigned d = 0;
       // act() and the granule controller form: the answer granules themselves, every tag =
       // this request's epoch; the r04 / multi-workgroup controller forms: a done word
       // behind the drained outputs
-      const bool gran = !ctl || ctl_gran_ok;
+      const bool gran = !ctl || res_ctl == ResForm::Act1;
+      // a scan of the whole answer from its start: true when the kernel served this request
+      auto answered = [&] {
+        GranScan all = gran_scan(ctl != nullptr, batch, flags);
+        return gran_done(all, e0);
+      };
       if (!gran) {
-        for (unsigned it = 0; (d = __atomic_load_n(h_done, __ATOMIC_ACQUIRE)) != e0 && d != GO2PI_RES_LEAVE; ++it) {
-          __builtin_ia32_pause();
-          if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-        }
+        spin_until([&] { return (d = __atomic_load_n(h_done, __ATOMIC_ACQUIRE)) == e0 || d == GO2PI_RES_LEAVE; });
       } else {
-        GranScan sc = gran_scan(ctl != nullptr, batch, flags);
-        for (unsigned it = 0;; ++it) {
+        GranScan sc = gran_scan(ctl != nullptr, batch, flags);  // (resumes where it stopped)
+        spin_until([&] {
           if (gran_done(sc, e0)) {
             d = e0;
-            break;
+            return true;
           }
-          if ((d = __atomic_load_n(h_done, __ATOMIC_ACQUIRE)) == GO2PI_RES_LEAVE) {
-            // the kernel may have answered this request and then left (a LEAVE header
-            // from evict_residents, or a moved yield counter): its answer granules are
-            // acknowledged before the LEAVE done word (resident.hip: vmcnt(0), barrier,
-            // then done), so a rescan after seeing LEAVE finds them if it served the
-            // request. Treating a served request as unserved would run it twice: for a
-            // GRU / LSTM policy, advancing the hidden state twice.
-            GranScan again = gran_scan(ctl != nullptr, batch, flags);
-            if (gran_done(again, e0)) d = e0;
-            break;
-          }
-          __builtin_ia32_pause();
-          if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-        }
-        if (d == e0 && !ctl) act_take(batch);
+          if ((d = __atomic_load_n(h_done, __ATOMIC_ACQUIRE)) != GO2PI_RES_LEAVE) return false;
+          // the kernel may have answered this request and then left (a LEAVE header
+          // from evict_residents, or a moved yield counter): its answer granules are
+          // acknowledged before the LEAVE done word (resident.hip: vmcnt(0), barrier,
+          // then done), so a rescan after seeing LEAVE finds them if it served the
+          // request. Treating a served request as unserved would run it twice: for a
+          // GRU / LSTM policy, advancing the hidden state twice.
+          if (answered()) d = e0;
+          return true;
+        });
       }
       res_last = std::chrono::steady_clock::now();
-      if (d == e0) return true;
-      // the kernel left: wait for it to drain. An idle exit racing this request is
-      // benign (serve it from a fresh launch with a fresh epoch); a hand-off timeout
-      // (h_err set) is a device-side protocol fault and is reported, not retried
-      need_device();
-      resident_stop();
-      if (gran) {  // the kernel has exited (stream synced): a request it served has every granule
-        GranScan again = gran_scan(ctl != nullptr, batch, flags);
-        if (gran_done(again, e0)) {
-          if (!ctl) act_take(batch);
-          return true;
-        }
+      bool served = d == e0;
+      if (!served) {
+        // the kernel left: wait for it to drain. An idle exit racing this request is
+        // benign (serve it from a fresh launch with a fresh epoch); a hand-off timeout
+        // (h_err set) is a device-side protocol fault and is reported, not retried
+        need_device();
+        resident_stop();
+        // the kernel has exited (stream synced): a request it served has every granule
+        served = gran && answered();
+      }
+      if (served) {
+        if (!ctl) act_take(batch);
+        return true;
       }
       if (__atomic_load_n(h_err, __ATOMIC_ACQUIRE)) {
         __atomic_store_n(h_err, 0u, __ATOMIC_RELEASE);
@@ -582,6 +637,15 @@ struct go2pi_engine {
       __atomic_store_n(h_err + 64, 0u, __ATOMIC_RELEASE);
       throw HipError("batched kernel: a layer hand-off between waves timed out (outputs invalid)", GO2PI_E_DEVICE);
     }
+  }
+
+  // act() by the resident kernel, the action into the caller's buffer; false: not served
+  // (resident_serve)
+  bool resident_act(const float *obs, float *act, int64_t batch) {
+    if (!resident_serve(nullptr, obs, batch, 0u)) return false;
+    check_handoff();
+    std::memcpy(act, h_act, sizeof(float) * (size_t)batch * model.out_dim);
+    return true;
   }
 
   // Enqueue one controller tick (device-accessible pointers in c).
@@ -767,7 +831,7 @@ bool w4_eligible(const go2pi_engine &e, const go2pi::Model &m) {
   if (!(e.opts.waves == 0 || e.opts.waves == 4) || nl < 2) return false;
   if (m.has_gru && m.gru.H % 64) return false;
   if (m.has_gru && m.gru.cell == 0 && m.gru.lbr == 0) return false;  // the two-pass cell: generic body only
-  if (std::getenv("GO2PI_NO_HEAD_FUSE") || std::getenv("GO2PI_NO_W4")) return false;  // env: A/B diagnostics only
+  if (e.sw.no_head_fuse || e.sw.no_w4) return false;  // A/B diagnostics only
   if (has_ln(m)) return false;  // LayerNormalization: the general body only (fused_impl.hpp ln_tile)
   const int tpw = ceil64(m.layers[0].N) / 64, t_last = ceil16(m.layers[nl - 1].N) / 16;
   if (!(tpw == 2 || tpw == 4 || tpw == 8) || t_last > (tpw == 8 ? 1 : 2)) return false;
@@ -782,6 +846,7 @@ bool w4_eligible(const go2pi_engine &e, const go2pi::Model &m) {
 bool ln_small_on(const go2pi_engine &e) { return e.opts.ln_small == 1; }
 
 void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o) {
+  const Switches &sw = e.sw = Switches::read();
   go2pi_default_opts(&e.opts);
   if (o) {
     if (o->struct_size < (int32_t)offsetof(go2pi_opts, obs_mean))
@@ -833,8 +898,8 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   // a 48- or 98-wide observation is padded to 16 columns, not 64 (25 % / 12.5 %
   // fewer layer-0 MFMAs and fragment bytes). Other kernels take any chunk count.
   const bool w4_shape = w4_eligible(e, m);
-  const int k0q = (w4_shape && !m.has_gru && (ceil16(m.layers[0].K) / 16) % 4 == 3 && !std::getenv("GO2PI_K0_PAD64"))
-                      ? 16 : 64;  // env: A/B diagnostics only
+  const int k0q = (w4_shape && !m.has_gru && (ceil16(m.layers[0].K) / 16) % 4 == 3 && !sw.k0_pad64)
+                      ? 16 : 64;  // (the switch: A/B diagnostics only)
   // every dense layer's fragments back to back in one arena (the pipeline finds
   // layer l from the base: fused_impl.hpp w4_layer_w)
   std::vector<std::vector<float>> packed(p.nl);
@@ -928,7 +993,7 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   p.zero_fill = (m.has_gru && m.gru.H % 64) ? 1 : 0;
   // head fusion: a narrow final layer (<= 2 tiles) whose predecessor runs one tile
   // group set per wave (T >= waves) is folded into the predecessor's epilogue
-  if (p.nl >= 2 && !std::getenv("GO2PI_NO_HEAD_FUSE")) {  // env: A/B diagnostics only
+  if (p.nl >= 2 && !sw.no_head_fuse) {  // (the switch: A/B diagnostics only)
     const int t_last = p.L[p.nl - 1].N_pad / 16, t_prev = p.L[p.nl - 2].N_pad / 16;
     // (not behind a LayerNormalization: dense_layer_head feeds the head from un-normalised registers)
     if (t_last <= 2 && t_prev >= e.waves && !p.L[p.nl - 2].ln) p.head_fuse = t_last;
@@ -1012,24 +1077,24 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   e.palloc(&e.h_obs, &e.m_obs, sizeof(float) * GO2PI_SMALL_MAXB * m.in_dim);
   e.palloc(&e.h_act, &e.m_act, sizeof(float) * GO2PI_SMALL_MAXB * m.out_dim);
 
+  const bool ln = has_ln(m);
+  // a layer past the first with more than 512 input columns: at batch 5 and up its input
+  // rows pass the 4096 granules one sweep round takes. The single launch and the
+  // resident act() form sweep a second round (their general instantiations,
+  // program.hpp program_small_general); the resident controller and recurrent forms do not
+  int kmax1 = 0;
+  for (int l = 1; l < p.nl; ++l) kmax1 = std::max(kmax1, p.L[l].K_pad);
+  const bool one_round = kmax1 <= 512;
   // single-launch small-batch path: dense programs whose layers fit the kernel's
   // register slots (K_pad <= 1024) and whose widest layer fits one resident grid
   {
     int kmax = 0;
     for (int l = 0; l < p.nl; ++l) kmax = std::max(kmax, p.L[l].K_pad);
     const bool lat_shape = kmax <= 1024 && go2pi::latency_grid(p) <= 256 && e.small_batch > 0 &&
-                           !std::getenv("GO2PI_SMALL_CHAIN");  // env: diagnostics, force the GEMV chain
+                           !sw.small_chain;  // (the switch: diagnostics, force the GEMV chain)
     // (a LayerNormalization policy: only with opts.ln_small; latency_body normalises the
     // swept rows as gemv_layer_kernel does)
-    const bool ln = has_ln(m);
     e.latency_ok = !m.has_gru && lat_shape && (!ln || ln_small_on(e));
-    // a layer past the first with more than 512 input columns: at batch 5 and up its input
-    // rows pass the 4096 granules one sweep round takes. The single launch and the
-    // resident act() form sweep a second round (their general instantiations,
-    // program.hpp program_small_general); the resident controller and recurrent forms do not
-    int kmax1 = 0;
-    for (int l = 1; l < p.nl; ++l) kmax1 = std::max(kmax1, p.L[l].K_pad);
-    const bool one_round = kmax1 <= 512;
     // the resident kernel's GRU / LSTM form (resident.hip, RNN): the cell tiled in front
     // of the dense layers, h' carried between requests as granules (an LSTM's c in the
     // owning workgroups' LDS)
@@ -1053,7 +1118,7 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
       // room for a controller tick's rows too (GO2PI_CTL_RAW + in_dim floats per robot)
       const size_t nreq = 1 + GO2PI_SMALL_MAXB * (size_t)(m.in_dim + GO2PI_CTL_RAW);
       size_t rb = sizeof(unsigned long long) * nreq;
-      if (void *bar = bar_take(e.device, rb)) {  // large BAR: the ring in VRAM, written by the host
+      if (void *bar = bar_take(e.device, rb, sw.req_host)) {  // large BAR: the ring in VRAM, written by the host
         e.h_req = e.m_req = static_cast<unsigned long long *>(bar);
         e.req_bar_bytes = rb;
       } else {
@@ -1069,19 +1134,13 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
       e.res_idle_ticks = (unsigned long long)e.opts.resident_ms * (unsigned long long)khz;
       e.resident_ok = true;
       res_register(&e);
-      // the controller-tick form serves dense policies without LayerNormalization (an LN
-      // policy's tick at batch <= 8: policy_latency_ctl_kernel)
-      e.resident_ctl_ok = !m.has_gru && !ln && one_round;
     }
   }
   // GO2PI_EPOCH0=<u32>: the engine's first granule tag instead of 1 (diagnostics and tests: a
   // value near 2^32 puts the tag-space wrap of next_epoch / resident_serve a few calls away
   // instead of ~1e9; 0, the empty granule's tag, is ignored)
-  if (const char *s = std::getenv("GO2PI_EPOCH0")) {
-    const unsigned long long v = std::strtoull(s, nullptr, 0);
-    if (v >= 1 && v <= 0xFFFFFFFFull) e.epoch = (unsigned)v;
-  }
-  if (std::getenv("GO2PI_DIAG_STAMPS")) {  // diagnostics: per-workgroup clock stamps
+  if (sw.epoch0) e.epoch = sw.epoch0;
+  if (sw.diag_stamps) {  // diagnostics: per-workgroup clock stamps
     e.n_stamps = GO2PI_STAMPS_PER_WG * ((e.opts.max_batch + GO2PI_TILE_ROWS - 1) / GO2PI_TILE_ROWS);
     p.stamps = e.dalloc<unsigned long long>(e.n_stamps);
     hip_check(hipMemsetAsync(p.stamps, 0, e.n_stamps * sizeof(unsigned long long), e.stream), "hipMemsetAsync");
@@ -1128,48 +1187,55 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
     // LDS row no wider than the hidden layers
     p.w4_plain = !p.has_gru && !p.pre_sub && !p.pre_div && !p.pre_mul && !p.pre_clip && !p.post_tanh &&
                  std::isinf(p.clip_lo) && p.clip_lo < 0 && std::isinf(p.clip_hi) && p.clip_hi > 0 &&
-                 p.scale == 1.f && p.lds_stride == 64 * p.w4_tpw + 4 && !std::getenv("GO2PI_NO_PLAIN");
+                 p.scale == 1.f && p.lds_stride == 64 * p.w4_tpw + 4 && !sw.no_plain;
     // the lean kernel's compile-time activation: Elu (the exported rsl_rl / Isaac policies'), else runtime
     // (1 = Elu with alpha 1, the ONNX default; any other alpha takes the runtime form)
-    p.w4_actc = (p.hid_act == 1 && p.hid_alpha == 1.f && !std::getenv("GO2PI_LEAN_RT_ACT")) ? 1 : -1;  // env: A/B only
+    p.w4_actc = (p.hid_act == 1 && p.hid_alpha == 1.f && !sw.lean_rt_act) ? 1 : -1;  // (the switch: A/B only)
     // ... and its hidden-layer count (3: the usual policy depth): the layer loop fully
     // unrolled, so no ring-register copies (and no vmcnt(0)) at the layer boundaries.
     // The general body (recurrent policies) takes both only together.
-    p.w4_nhc = (p.w4_actc == 1 && p.nl - 1 == 3 && !std::getenv("GO2PI_LEAN_RT_NH")) ? 3 : 0;  // env: A/B only
+    p.w4_nhc = (p.w4_actc == 1 && p.nl - 1 == 3 && !sw.lean_rt_nh) ? 3 : 0;  // (the switch: A/B only)
     if (!p.w4_plain && p.w4_nhc == 0) p.w4_actc = -1;
     // the lean recurrent tick (policy_gru_kernel, r05; policy_lstm_kernel, r06): a GRU cell
     // (lbr = 1) or an LSTM cell in front of a dense chain the lean kernel would serve
-    // (gru_lean_on: GO2PI_GRU_GENERAL=1 keeps the general body for both cells, A/B)
+    // (GO2PI_GRU_GENERAL=1 keeps the general body for both cells, A/B)
     p.w4_gru_lean = (p.has_gru && ((p.gru.cell == 0 && p.gru.lbr == 1) || p.gru.cell == 1) &&
                      (p.gru.H == 128 || p.gru.H == 256) &&
                      p.gru.H <= 64 * p.w4_tpw && !p.pre_sub && !p.pre_div && !p.pre_mul && !p.pre_clip &&
                      p.post_plain && p.lds_stride == 64 * p.w4_tpw + 4 && p.w4_actc == 1 && p.w4_nhc == 3 &&
                      p.c0 == p.gru.H / 16 && p.gru.I_pad == (p.in_dim + 63) / 64 * 64 && p.in_dim < 4096 &&
-                     !p.zero_fill && gru_lean_on()) ? 1 : 0;
+                     !p.zero_fill && !sw.gru_general) ? 1 : 0;
   }
-  // a dense policy whose weights fit one CU's registers is served by the single-
-  // workgroup resident kernel (no inter-workgroup hop per layer; GO2PI_RES_MULTI=1:
-  // the multi-workgroup form, A/B diagnostics)
-  e.resident1 = e.resident_ok && !m.has_gru && go2pi::resident1_fits(p, false) && !std::getenv("GO2PI_RES_MULTI");
-  e.resident1_ctl = e.resident_ok && !m.has_gru && go2pi::resident1_fits(p, true) && !std::getenv("GO2PI_RES_MULTI");
-  // a LayerNormalization policy (opts.ln_small): policy_act1_kernel's act() form where its
-  // shape applies, never r04's policy_resident1_kernel (also under GO2PI_RES_R1W=1, which
-  // then selects the multi-workgroup form) and no single-workgroup controller form
-  if (has_ln(m)) {
-    e.resident1 = e.resident_ok && go2pi::resident1_ctl_granules(p) && !std::getenv("GO2PI_RES_MULTI");
-    e.resident1_ctl = false;
-  }
-  e.ctl_gran_ok = e.resident1_ctl && go2pi::resident1_ctl_granules(p);
   // the controller tick's general body instead of the lean tick kernel (A/B diagnostics,
   // tests/test_gpu_controller.py::test_controller_tick_bodies)
-  p.ctl_general = std::getenv("GO2PI_CTL_GENERAL") != nullptr ? 1 : 0;
-  // a wide dense policy (every hidden layer 256 or 512 wide: BASELINE configs[1]'s
-  // 48 -> 512^3 -> 12) is served by policy_wide_kernel when every workgroup can poll the
-  // request ring in device memory (large BAR); else by the multi-workgroup kernel, whose
-  // workgroup 0 alone polls the host and mirrors the request (GO2PI_RES_MULTI=1: that
-  // form regardless, A/B and its tests)
-  e.wide = e.resident_ok && !e.resident1 && !m.has_gru && !has_ln(m) && e.req_bar_bytes > 0 &&
-           go2pi::wide_shape(p).nl > 0 && !std::getenv("GO2PI_RES_MULTI");
+  p.ctl_general = sw.ctl_general ? 1 : 0;
+  // The resident kernel of each kind of request (program.hpp ResForm), decided here and
+  // nowhere else. Every policy with a resident path has the multi-workgroup kernel; a
+  // dense one takes a better form where one applies (GO2PI_RES_MULTI=1: never, A/B and
+  // the multi-workgroup form's tests):
+  //  - one workgroup, where the weights fit one CU's registers (no inter-workgroup hop per
+  //    layer): policy_act1_kernel wherever its shape applies (GO2PI_RES_R1W=1: never), else
+  //    r04's policy_resident1_kernel where that fits;
+  //  - act() of a wide policy (every hidden layer 256 or 512 wide: BASELINE configs[1]'s
+  //    48 -> 512^3 -> 12): policy_wide_kernel, when every workgroup can poll the request
+  //    ring in device memory (large BAR); else workgroup 0 of the multi-workgroup kernel
+  //    alone polls the host and mirrors the request.
+  // A LayerNormalization policy (opts.ln_small): of these, policy_act1_kernel's act() form
+  // only, and no resident controller form (its tick at batch <= 8: policy_latency_ctl_kernel).
+  // The controller form serves dense policies whose layer inputs fit one sweep round.
+  if (e.resident_ok) {
+    const bool better = !m.has_gru && !sw.res_multi;
+    const bool act1 = better && !sw.res_r1w && go2pi::resident_act1_fits(p);
+    e.res_act = ResForm::Multi;
+    if (act1) e.res_act = ResForm::Act1;
+    else if (better && !ln && go2pi::resident_r1_fits(p, false)) e.res_act = ResForm::R1;
+    else if (better && !ln && e.req_bar_bytes > 0 && go2pi::wide_shape(p).nl > 0) e.res_act = ResForm::Wide;
+    if (!m.has_gru && !ln && one_round) {
+      e.res_ctl = ResForm::Multi;
+      if (act1) e.res_ctl = ResForm::Act1;
+      else if (better && go2pi::resident_r1_fits(p, true)) e.res_ctl = ResForm::R1;
+    }
+  }
   hip_check(go2pi::configure_kernels(p, e.waves), "hipFuncSetAttribute");
   e.d_prog = e.dalloc<go2pi::DevProgram>(1);
   hip_check(hipMemcpy(e.d_prog, &p, sizeof(p), hipMemcpyHostToDevice), "hipMemcpy");
@@ -1198,6 +1264,9 @@ int guarded_nodev(F &&f) {
   } catch (const HipError &ex) {
     g_last_error = ex.what();
     return ex.code;
+  } catch (const std::bad_alloc &) {
+    g_last_error = "out of host memory";
+    return GO2PI_E_INVALID;
   } catch (const std::exception &ex) {
     g_last_error = ex.what();
     return GO2PI_E_INVALID;
@@ -1207,22 +1276,7 @@ int guarded_nodev(F &&f) {
 template <class F>
 int guarded(F &&f) {
   DeviceRestore keep;
-  try {
-    g_last_error.clear();
-    return f();
-  } catch (const ApiError &ex) {
-    g_last_error = ex.what();
-    return ex.code;
-  } catch (const HipError &ex) {
-    g_last_error = ex.what();
-    return ex.code;
-  } catch (const std::bad_alloc &) {
-    g_last_error = "out of host memory";
-    return GO2PI_E_INVALID;
-  } catch (const std::exception &ex) {
-    g_last_error = ex.what();
-    return GO2PI_E_INVALID;
-  }
+  return guarded_nodev(f);
 }
 
 void check_engine(const go2pi_engine *e) {
@@ -1350,14 +1404,7 @@ int go2pi_run(go2pi_engine *e, const float *obs, float *act, int64_t batch) {
   if (e && obs && act && batch >= 1 && batch <= GO2PI_SMALL_MAXB && batch <= e->opts.max_batch && e->resident_ok &&
       e->resident_ready(nullptr)) {
     e->lazy_dev = true;
-    const int rc = guarded_nodev([&] {
-      const bool ok = e->resident_serve(nullptr, obs, batch, 0u);
-      if (ok) {
-        e->check_handoff();
-        std::memcpy(act, e->h_act, sizeof(float) * (size_t)batch * e->model.out_dim);
-      }
-      return ok ? GO2PI_OK : 1;
-    });
+    const int rc = guarded_nodev([&] { return e->resident_act(obs, act, batch) ? GO2PI_OK : 1; });
     e->dev_done();
     if (rc != 1) return rc;
     res_try = false;  // not served (evicted twice): a launch serves it
@@ -1368,11 +1415,7 @@ int go2pi_run(go2pi_engine *e, const float *obs, float *act, int64_t batch) {
     if (batch == 0) return GO2PI_OK;
     if (!obs || !act) throw ApiError("null obs/act buffer", GO2PI_E_INVALID);
     hip_check(hipSetDevice(e->device), "hipSetDevice");
-    if (res_try && e->resident_ok && batch <= GO2PI_SMALL_MAXB && e->resident_serve(nullptr, obs, batch, 0u)) {
-      e->check_handoff();
-      std::memcpy(act, e->h_act, sizeof(float) * (size_t)batch * e->model.out_dim);
-      return GO2PI_OK;
-    }
+    if (res_try && e->resident_ok && batch <= GO2PI_SMALL_MAXB && e->resident_act(obs, act, batch)) return GO2PI_OK;
     e->resident_stop();
     std::unique_lock<std::mutex> ev;  // (held until the launch below is enqueued)
     if (batch > GO2PI_SMALL_MAXB || !e->latency_ok) ev = evict_residents(e, batch);  // a batched (fused) launch follows
@@ -1546,6 +1589,8 @@ int go2pi_ctl_set_params(go2pi_engine *e, const go2pi_ctl_params *p) {
   });
 }
 
+}  // extern "C"
+
 namespace {
 // byte offsets of the controller staging buffers for `rows` robots (256 B aligned)
 struct CtlLayout {
@@ -1570,7 +1615,88 @@ void check_ctl(const go2pi_engine *e, int64_t batch) {
   check_batch(e, batch);
   if (!e->ctl_hist) throw ApiError("policy I/O is not a Go2 controller's (need 49*k obs, 12 actions)", GO2PI_E_MODEL);
 }
+
+// One go2pi_controller_step call: the caller's rows, their byte counts, and how they
+// travel (the staging laid out by a CtlLayout, or the resident kernel's request). On the
+// stack: go2pi_controller_step's fast path allocates nothing.
+struct CtlCall {
+  const float *state, *joy;
+  float *obs, *action;
+  double *q_des, *kp, *kd;
+  uint32_t *status;
+  int64_t batch;
+  int in_dim;
+  size_t n_state = sizeof(float) * batch * GO2PI_CTL_STATE_DIM, n_joy = sizeof(float) * batch * GO2PI_CTL_JOY_DIM;
+  size_t n_obs = sizeof(float) * batch * in_dim, n_act = sizeof(float) * batch * GO2PI_CTL_DOF;
+  size_t n_d = sizeof(double) * batch * GO2PI_CTL_DOF, n_st = sizeof(uint32_t) * batch;
+
+  // the optional rows this call passed, as the resident request's header says it
+  unsigned flags() const {
+    return (joy ? GO2PI_RES_JOY : 0u) | (q_des ? GO2PI_RES_QDES : 0u) | (kp ? GO2PI_RES_KP : 0u) |
+           (kd ? GO2PI_RES_KD : 0u) | (status ? GO2PI_RES_STATUS : 0u);
+  }
+  // the resident request's rows: state | joystick | obs | action (no joystick: zeros)
+  void pack(float *rows) const {
+    std::memcpy(rows, state, n_state);
+    if (joy) std::memcpy(rows + batch * GO2PI_CTL_STATE_DIM, joy, n_joy);
+    else std::memset(rows + batch * GO2PI_CTL_STATE_DIM, 0, n_joy);
+    std::memcpy(rows + batch * (GO2PI_CTL_STATE_DIM + GO2PI_CTL_JOY_DIM), obs, n_obs);
+    std::memcpy(rows + batch * (GO2PI_CTL_STATE_DIM + GO2PI_CTL_JOY_DIM + in_dim), action, n_act);
+  }
+  // The kernels' view of the staging at `dev`. all: every optional row has its place (the
+  // resident kernel's controller form: the request's flags say which this call passed);
+  // else the optional rows as passed.
+  go2pi::DevCtl view(const go2pi::DevCtlParams *prm, char *dev, const CtlLayout &L, bool all) const {
+    go2pi::DevCtl c{};
+    c.prm = prm;
+    c.state = reinterpret_cast<const float *>(dev + L.state);
+    c.joy = (all || joy) ? reinterpret_cast<const float *>(dev + L.joy) : nullptr;
+    c.obs = reinterpret_cast<float *>(dev + L.obs);
+    c.action = reinterpret_cast<float *>(dev + L.action);
+    c.q_des = (all || q_des) ? reinterpret_cast<double *>(dev + L.q_des) : nullptr;
+    c.kp = (all || kp) ? reinterpret_cast<double *>(dev + L.kp) : nullptr;
+    c.kd = (all || kd) ? reinterpret_cast<double *>(dev + L.kd) : nullptr;
+    c.status = (all || status) ? reinterpret_cast<uint32_t *>(dev + L.status) : nullptr;
+    return c;
+  }
+  // the inputs into the staging: put(offset, source, bytes)
+  template <class F>
+  void put(const CtlLayout &L, F &&f) const {
+    f(L.state, state, n_state);
+    if (joy) f(L.joy, joy, n_joy);
+    f(L.obs, obs, n_obs);
+    f(L.action, action, n_act);
+  }
+  // the answers out of the staging: take(destination, offset, bytes)
+  template <class F>
+  void take(const CtlLayout &L, F &&f) const {
+    f(obs, L.obs, n_obs);
+    f(action, L.action, n_act);
+    if (q_des) f(q_des, L.q_des, n_d);
+    if (kp) f(kp, L.kp, n_d);
+    if (kd) f(kd, L.kd, n_d);
+    if (status) f(status, L.status, n_st);
+  }
+  void take_host(const CtlLayout &L, const char *stage) const {
+    take(L, [&](void *dst, size_t off, size_t n) { std::memcpy(dst, stage + off, n); });
+  }
+};
+
+// The tick by the resident kernel's controller form (batch <= GO2PI_SMALL_MAXB; all: the
+// all-rows view of the pinned staging, laid out by L), its answers into the caller's
+// buffers; false: not served (resident_serve). No HIP runtime call while a live kernel serves it.
+bool resident_tick(go2pi_engine *e, const CtlCall &c, const CtlLayout &L, const go2pi::DevCtl &all) {
+  float *rows = e->res_rows.data();
+  c.pack(rows);
+  if (!e->resident_serve(&all, rows, c.batch, c.flags())) return false;
+  e->check_handoff();
+  if (e->res_ctl == ResForm::Act1) e->ctl_take(c.batch, c.obs, c.action, c.q_des, c.kp, c.kd, c.status);
+  else c.take_host(L, e->h_ctl);
+  return true;
+}
 }  // namespace
+
+extern "C" {
 
 int go2pi_controller_step(go2pi_engine *e, const float *state, const float *joy, float *obs, float *action,
                           double *q_des, double *kp, double *kd, uint32_t *status, int64_t batch) {
@@ -1582,48 +1708,13 @@ int go2pi_controller_step(go2pi_engine *e, const float *state, const float *joy,
   // the guarded path below starts.
   bool res_try = true;
   if (e && state && obs && action && batch >= 1 && batch <= GO2PI_SMALL_MAXB && batch <= e->opts.max_batch &&
-      e->ctl_hist && e->resident_ok && e->resident_ctl_ok && e->done_ok && e->h_ctl) {
-    const int in_dim = e->model.in_dim;
-    const CtlLayout L(GO2PI_SMALL_MAXB, in_dim);
-    go2pi::DevCtl all{};
-    all.prm = e->d_ctl;
-    char *dev = e->m_ctl;
-    all.state = reinterpret_cast<const float *>(dev + L.state);
-    all.joy = reinterpret_cast<const float *>(dev + L.joy);
-    all.obs = reinterpret_cast<float *>(dev + L.obs);
-    all.action = reinterpret_cast<float *>(dev + L.action);
-    all.q_des = reinterpret_cast<double *>(dev + L.q_des);
-    all.kp = reinterpret_cast<double *>(dev + L.kp);
-    all.kd = reinterpret_cast<double *>(dev + L.kd);
-    all.status = reinterpret_cast<uint32_t *>(dev + L.status);
+      e->ctl_hist && e->res_ctl != ResForm::None && e->h_ctl) {
+    const CtlCall c{state, joy, obs, action, q_des, kp, kd, status, batch, e->model.in_dim};
+    const CtlLayout L(GO2PI_SMALL_MAXB, c.in_dim);
+    const go2pi::DevCtl all = c.view(e->d_ctl, e->m_ctl, L, true);
     if (e->resident_ready(&all)) {
       e->lazy_dev = true;
-      const int rc = guarded_nodev([&] {
-        const size_t n_state = sizeof(float) * batch * GO2PI_CTL_STATE_DIM, n_joy = sizeof(float) * batch * GO2PI_CTL_JOY_DIM;
-        const size_t n_obs = sizeof(float) * batch * in_dim, n_act = sizeof(float) * batch * GO2PI_CTL_DOF;
-        const size_t n_d = sizeof(double) * batch * GO2PI_CTL_DOF, n_st = sizeof(uint32_t) * batch;
-        const unsigned flags = (joy ? GO2PI_RES_JOY : 0u) | (q_des ? GO2PI_RES_QDES : 0u) | (kp ? GO2PI_RES_KP : 0u) |
-                               (kd ? GO2PI_RES_KD : 0u) | (status ? GO2PI_RES_STATUS : 0u);
-        float *rows = e->res_rows.data();  // state | joystick | obs | action
-        std::memcpy(rows, state, n_state);
-        if (joy) std::memcpy(rows + batch * GO2PI_CTL_STATE_DIM, joy, n_joy);
-        else std::memset(rows + batch * GO2PI_CTL_STATE_DIM, 0, n_joy);
-        std::memcpy(rows + batch * (GO2PI_CTL_STATE_DIM + GO2PI_CTL_JOY_DIM), obs, n_obs);
-        std::memcpy(rows + batch * (GO2PI_CTL_STATE_DIM + GO2PI_CTL_JOY_DIM + in_dim), action, n_act);
-        if (!e->resident_serve(&all, rows, batch, flags)) return 1;
-        e->check_handoff();
-        if (e->ctl_gran_ok) {
-          e->ctl_take(batch, obs, action, q_des, kp, kd, status);
-          return GO2PI_OK;
-        }
-        std::memcpy(obs, e->h_ctl + L.obs, n_obs);
-        std::memcpy(action, e->h_ctl + L.action, n_act);
-        if (q_des) std::memcpy(q_des, e->h_ctl + L.q_des, n_d);
-        if (kp) std::memcpy(kp, e->h_ctl + L.kp, n_d);
-        if (kd) std::memcpy(kd, e->h_ctl + L.kd, n_d);
-        if (status) std::memcpy(status, e->h_ctl + L.status, n_st);
-        return GO2PI_OK;
-      });
+      const int rc = guarded_nodev([&] { return resident_tick(e, c, L, all) ? GO2PI_OK : 1; });
       e->dev_done();
       if (rc != 1) return rc;
       res_try = false;  // not served (evicted twice): a launch serves it
@@ -1634,95 +1725,38 @@ int go2pi_controller_step(go2pi_engine *e, const float *state, const float *joy,
     if (batch == 0) return GO2PI_OK;
     if (!state || !obs || !action) throw ApiError("null state/obs/action buffer", GO2PI_E_INVALID);
     hip_check(hipSetDevice(e->device), "hipSetDevice");
-    const int in_dim = e->model.in_dim;
+    const CtlCall c{state, joy, obs, action, q_des, kp, kd, status, batch, e->model.in_dim};
     const bool small = batch <= GO2PI_SMALL_MAXB;
-    const CtlLayout L(small ? GO2PI_SMALL_MAXB : e->opts.max_batch, in_dim);
-    const size_t n_state = sizeof(float) * batch * GO2PI_CTL_STATE_DIM, n_joy = sizeof(float) * batch * GO2PI_CTL_JOY_DIM;
-    const size_t n_obs = sizeof(float) * batch * in_dim, n_act = sizeof(float) * batch * GO2PI_CTL_DOF;
-    const size_t n_d = sizeof(double) * batch * GO2PI_CTL_DOF, n_st = sizeof(uint32_t) * batch;
+    const CtlLayout L(small ? GO2PI_SMALL_MAXB : e->opts.max_batch, c.in_dim);
     char *dev;  // device-side view of the staging
     if (small) {
-      if (!e->h_ctl) {
-        e->palloc(&e->h_ctl, &e->m_ctl, L.total);
-      }
-      std::memcpy(e->h_ctl + L.state, state, n_state);
-      if (joy) std::memcpy(e->h_ctl + L.joy, joy, n_joy);
-      std::memcpy(e->h_ctl + L.obs, obs, n_obs);
-      std::memcpy(e->h_ctl + L.action, action, n_act);
+      if (!e->h_ctl) e->palloc(&e->h_ctl, &e->m_ctl, L.total);
+      c.put(L, [&](size_t off, const void *src, size_t n) { std::memcpy(e->h_ctl + off, src, n); });
       dev = e->m_ctl;
     } else {
       if (!e->d_ctlbuf) e->d_ctlbuf = e->dalloc<char>(L.total);
       dev = e->d_ctlbuf;
-      auto h2d = [&](size_t off, const void *src, size_t n) {
+      c.put(L, [&](size_t off, const void *src, size_t n) {
         hip_check(hipMemcpyAsync(dev + off, src, n, hipMemcpyHostToDevice, e->stream), "hipMemcpyAsync H2D");
-      };
-      h2d(L.state, state, n_state);
-      if (joy) h2d(L.joy, joy, n_joy);
-      h2d(L.obs, obs, n_obs);
-      h2d(L.action, action, n_act);
+      });
     }
-    go2pi::DevCtl c{};
-    c.prm = e->d_ctl;
-    c.state = reinterpret_cast<const float *>(dev + L.state);
-    c.joy = joy ? reinterpret_cast<const float *>(dev + L.joy) : nullptr;
-    c.obs = reinterpret_cast<float *>(dev + L.obs);
-    c.action = reinterpret_cast<float *>(dev + L.action);
-    c.q_des = q_des ? reinterpret_cast<double *>(dev + L.q_des) : nullptr;
-    c.kp = kp ? reinterpret_cast<double *>(dev + L.kp) : nullptr;
-    c.kd = kd ? reinterpret_cast<double *>(dev + L.kd) : nullptr;
-    c.status = status ? reinterpret_cast<uint32_t *>(dev + L.status) : nullptr;
-    const bool res = res_try && small && e->resident_ok && e->resident_ctl_ok && e->done_ok;
-    bool served = false;  // by the resident kernel
-    if (res) {
-      // the resident kernel's controller form: every optional row has its place in the
-      // staging; the header's flags say which this call passed
-      go2pi::DevCtl all = c;
-      all.joy = reinterpret_cast<const float *>(dev + L.joy);
-      all.q_des = reinterpret_cast<double *>(dev + L.q_des);
-      all.kp = reinterpret_cast<double *>(dev + L.kp);
-      all.kd = reinterpret_cast<double *>(dev + L.kd);
-      all.status = reinterpret_cast<uint32_t *>(dev + L.status);
-      const unsigned flags = (joy ? GO2PI_RES_JOY : 0u) | (q_des ? GO2PI_RES_QDES : 0u) | (kp ? GO2PI_RES_KP : 0u) |
-                             (kd ? GO2PI_RES_KD : 0u) | (status ? GO2PI_RES_STATUS : 0u);
-      float *rows = e->res_rows.data();  // state | joystick | obs | action
-      std::memcpy(rows, state, n_state);
-      if (joy) std::memcpy(rows + batch * GO2PI_CTL_STATE_DIM, joy, n_joy);
-      else std::memset(rows + batch * GO2PI_CTL_STATE_DIM, 0, n_joy);
-      std::memcpy(rows + batch * (GO2PI_CTL_STATE_DIM + GO2PI_CTL_JOY_DIM), obs, n_obs);
-      std::memcpy(rows + batch * (GO2PI_CTL_STATE_DIM + GO2PI_CTL_JOY_DIM + in_dim), action, n_act);
-      served = e->resident_serve(&all, rows, batch, flags);
-    } else {
-      e->resident_stop();
-    }
-    const bool single = !served && small && e->use_latency(batch) && e->done_ok;
+    // the resident kernel's controller form (a request it does not serve: by a launch)
+    if (res_try && small && e->res_ctl != ResForm::None && resident_tick(e, c, L, c.view(e->d_ctl, dev, L, true)))
+      return GO2PI_OK;
+    e->resident_stop();
+    const bool single = small && e->use_latency(batch) && e->done_ok;
     std::unique_lock<std::mutex> ev;
-    if (!single && !served) ev = evict_residents(e, batch);  // a batched (fused) launch follows
-    if (!served) e->enqueue_ctl(c, batch, e->stream, single ? e->m_done : nullptr);
+    if (!single) ev = evict_residents(e, batch);  // a batched (fused) launch follows
+    e->enqueue_ctl(c.view(e->d_ctl, dev, L, false), batch, e->stream, single ? e->m_done : nullptr);
     if (ev.owns_lock()) ev.unlock();  // (the launch is enqueued)
     if (small) {
-      const bool synced = served || (single && e->spin_done());
-      if (!synced) hip_check(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+      if (!(single && e->spin_done())) hip_check(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
       e->check_handoff();
-      if (served && e->ctl_gran_ok) {
-        e->ctl_take(batch, obs, action, q_des, kp, kd, status);
-      } else {
-        std::memcpy(obs, e->h_ctl + L.obs, n_obs);
-        std::memcpy(action, e->h_ctl + L.action, n_act);
-        if (q_des) std::memcpy(q_des, e->h_ctl + L.q_des, n_d);
-        if (kp) std::memcpy(kp, e->h_ctl + L.kp, n_d);
-        if (kd) std::memcpy(kd, e->h_ctl + L.kd, n_d);
-        if (status) std::memcpy(status, e->h_ctl + L.status, n_st);
-      }
+      c.take_host(L, e->h_ctl);
     } else {
-      auto d2h = [&](void *dst, size_t off, size_t n) {
+      c.take(L, [&](void *dst, size_t off, size_t n) {
         hip_check(hipMemcpyAsync(dst, dev + off, n, hipMemcpyDeviceToHost, e->stream), "hipMemcpyAsync D2H");
-      };
-      d2h(obs, L.obs, n_obs);
-      d2h(action, L.action, n_act);
-      if (q_des) d2h(q_des, L.q_des, n_d);
-      if (kp) d2h(kp, L.kp, n_d);
-      if (kd) d2h(kd, L.kd, n_d);
-      if (status) d2h(status, L.status, n_st);
+      });
       hip_check(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
     }
     return GO2PI_OK;
@@ -1767,29 +1801,13 @@ int go2pi_get_cost(const go2pi_engine *e, go2pi_cost *c) {
   });
 }
 
-// the lean GRU tick wherever it applies (GO2PI_GRU_GENERAL=1: the general body, A/B;
-// r05 same-box A/B, GRU-256 at 4096 robots: 56.7 against 60.5-60.9 us per one-tick launch)
-static bool gru_lean_on() { return !std::getenv("GO2PI_GRU_GENERAL"); }
-
+// The reported kernel names are printed by the launcher modules, each from the dispatch
+// that launches (kernels.hip batched_kernel_name, resident.hip resident_kernel_name).
 int go2pi_batched_kernel(const go2pi_engine *e, char *buf, size_t cap) {
   return guarded([&] {
     check_engine(e);
     if (!buf || cap == 0) throw ApiError("null buffer", GO2PI_E_INVALID);
-    const int t = e->waves == 4 ? e->prog.w4_tpw : 0, h = t ? e->prog.head_fuse : 0;
-    const int c0m = t ? e->prog.w4_c0m : 0;
-    if (t && e->prog.w4_gru_lean)  // the lean GRU / LSTM tick: <tiles per wave, head tiles, hidden tiles per wave>
-      std::snprintf(buf, cap, "%s<%d, %d, %d>", e->prog.gru.cell == 1 ? "policy_lstm_kernel" : "policy_gru_kernel", t,
-                    h, e->prog.gru.H / 64);
-    else if (t && e->prog.w4_plain)  // the lean pipeline kernel: <tiles per wave, head tiles, layer-0 chunks mod 4,
-                                     // act, hidden layers, waves per workgroup (4)>
-      // (what a one-tick launch runs: the one-tick form, or the looped one for a head with an activation)
-      std::snprintf(buf, cap, "%s<%d, %d, %d, %d, %d, 4>",
-                    e->prog.head_act == 0 ? "policy_mlp_kernel" : "policy_mlp_seq_kernel", t, h, c0m, e->prog.w4_actc,
-                    e->prog.w4_nhc);
-    else
-      std::snprintf(buf, cap, "policy_fused_kernel<%d, %d, %d, %d, %d, %d, %d>", e->waves, t, h, c0m,
-                    (e->prog.has_gru && e->prog.gru.cell == 1) ? 1 : 0, t ? e->prog.w4_actc : -1,
-                    t ? e->prog.w4_nhc : 0);
+    go2pi::batched_kernel_name(e->prog, e->waves, buf, cap);
     return GO2PI_OK;
   });
 }
@@ -1798,18 +1816,7 @@ int go2pi_resident_kernel(const go2pi_engine *e, char *buf, size_t cap) {
   return guarded([&] {
     check_engine(e);
     if (!buf || cap == 0) throw ApiError("null buffer", GO2PI_E_INVALID);
-    const char *ring = e->req_bar_bytes ? " ring=vram" : " ring=host";
-    if (!e->resident_ok) {
-      std::snprintf(buf, cap, "none");
-    } else if (e->resident1) {
-      std::snprintf(buf, cap, "%s%s",
-                    go2pi::resident1_ctl_granules(e->prog) ? "policy_act1_kernel" : "policy_resident1_kernel", ring);
-    } else if (e->wide) {
-      const go2pi::WideShape w = go2pi::wide_shape(e->prog);  // (what launch_resident_wide runs)
-      std::snprintf(buf, cap, "policy_wide_kernel<%d, %d, %d, %d>%s", w.nl, w.cw, w.f0, w.pro, ring);
-    } else {
-      std::snprintf(buf, cap, "policy_resident_kernel%s", ring);
-    }
+    go2pi::resident_kernel_name(e->res_act, e->prog, e->req_bar_bytes > 0, buf, cap);
     return GO2PI_OK;
   });
 }
@@ -1820,10 +1827,10 @@ int go2pi_small_kernel(const go2pi_engine *e, char *buf, size_t cap) {
   return guarded([&] {
     check_engine(e);
     if (!buf || cap == 0) throw ApiError("null buffer", GO2PI_E_INVALID);
-    if (e->latency_ok)  // (an LN program's instantiation of it: policy_latency_ln_kernel)
-      std::snprintf(buf, cap, "policy_latency_kernel");
+    if (e->latency_ok)
+      std::snprintf(buf, cap, "%s", go2pi::latency_kernel_name());
     else
-      std::snprintf(buf, cap, e->opts.use_graph ? "gemv_layer_kernel graph" : "gemv_layer_kernel");
+      std::snprintf(buf, cap, "%s%s", go2pi::gemv_kernel_name(), e->opts.use_graph ? " graph" : "");
     return GO2PI_OK;
   });
 }

@@ -2220,6 +2220,8 @@ template <int TPW>
 int w4_launch(const DevProgram &p, const DevProgram *p_dev, const float *obs, float *act, float *hidden, int batch,
               int steps, void *stream);
 template <int TPW>
+int w4_name(const DevProgram &p, char *buf, size_t cap);  // w4_launch's kernel (batched_kernel_name)
+template <int TPW>
 int w4_launch_ctl(const DevProgram &p, const DevProgram *p_dev, const DevCtl &ctl, float *hidden, int batch,
                   void *stream);
 // The generic body's host side, one translation unit per wave count
@@ -2229,6 +2231,8 @@ int gen_configure(const DevProgram &p);
 template <int NW>
 int gen_launch(const DevProgram &p, const DevProgram *p_dev, const float *obs, float *act, float *hidden, int batch,
                int steps, void *stream);
+template <int NW>
+int gen_name(const DevProgram &p, char *buf, size_t cap);  // gen_launch's kernel
 template <int NW>
 int gen_launch_ctl(const DevProgram &p, const DevProgram *p_dev, const DevCtl &ctl, float *hidden, int batch,
                    void *stream);

@@ -452,6 +452,14 @@ int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves,
   });
 }
 
+int batched_kernel_name(const DevProgram &p, int waves, char *buf, size_t cap) {
+  if (waves == 4 && p.w4_tpw) return with_w4(p, [&](auto t) { return w4_name<decltype(t)::value>(p, buf, cap); });
+  return with_waves(waves, [&](auto w) { return gen_name<decltype(w)::value>(p, buf, cap); });
+}
+
+const char *latency_kernel_name() { return "policy_latency_kernel"; }
+const char *gemv_kernel_name() { return "gemv_layer_kernel"; }
+
 int launch_policy_fused_ctl(const DevProgram &p, const DevProgram *p_dev, int waves, const DevCtl &ctl,
                             float *hidden, int batch, void *stream) {
   if (batch <= 0) return 0;

@@ -43,6 +43,13 @@ int gen_launch<NW>(const DevProgram &p, const DevProgram *p_dev, const float *ob
 }
 
 template <>
+int gen_name<NW>(const DevProgram &p, char *buf, size_t cap) {  // (what gen_launch runs)
+  return with_rnn(p, [&]<int RNN>(std::integral_constant<int, RNN>) {
+    return std::snprintf(buf, cap, "policy_fused_kernel<%d, 0, 0, 0, %d, -1, 0>", NW, RNN);
+  });
+}
+
+template <>
 int gen_launch_ctl<NW>(const DevProgram &p, const DevProgram *p_dev, const DevCtl &ctl, float *hidden, int batch,
                        void *stream) {
   const dim3 grid((batch + GO2PI_TILE_ROWS - 1) / GO2PI_TILE_ROWS);

@@ -43,10 +43,12 @@ const void *batched_kernel() {
 // The lean recurrent tick's instantiation for program p (DevProgram::w4_gru_lean), or
 // null: the GRU tick (policy_gru_kernel) or the LSTM one (policy_lstm_kernel, r06), hidden
 // tiles per wave GT = H / 64 (2 or 4), the hidden rows no wider than the dense ones.
+// gt (optional): the instantiation's GT.
 template <int HT>
-const void *gru_lean_kernel(const DevProgram &p) {
+const void *gru_lean_kernel(const DevProgram &p, int *gt = nullptr) {
   if (!p.w4_gru_lean) return nullptr;
   const bool lstm = p.gru.cell == 1;
+  if (gt) *gt = p.gru.H == 128 ? 2 : 4;
   if (p.gru.H == 128)
     return lstm ? reinterpret_cast<const void *>(&policy_lstm_kernel<TPW, HT, 2>)
                 : reinterpret_cast<const void *>(&policy_gru_kernel<TPW, HT, 2>);
@@ -126,6 +128,27 @@ int w4_launch<TPW>(const DevProgram &p, const DevProgram *p_dev, const float *ob
                          reinterpret_cast<hipStream_t>(stream), p_dev, obs, act, hidden, batch, steps);
     }
     return (int)hipGetLastError();
+  });
+}
+
+// What w4_launch runs for one tick (steps = 1) of fewer than 2^20 rows, from the Shape it
+// launches: the same branches, a name where it has a launch.
+template <>
+int w4_name<TPW>(const DevProgram &p, char *buf, size_t cap) {
+  return with_shape(p, [&]<int HT, bool PL, int C0M, int RNN, int ACTC, int NHC>(Shape<HT, PL, C0M, RNN, ACTC, NHC>) {
+    if constexpr (PL) {
+      // <tiles per wave, head tiles, layer-0 chunks mod 4, act, hidden layers, waves per workgroup (4)>
+      return std::snprintf(buf, cap, "%s<%d, %d, %d, %d, %d, 4>",
+                           p.head_act == 0 ? "policy_mlp_kernel" : "policy_mlp_seq_kernel", TPW, HT, C0M, ACTC, NHC);
+    } else {
+      if constexpr (C0M == 0 && ACTC == 1 && NHC == 3) {
+        int gt = 0;
+        if (gru_lean_kernel<HT>(p, &gt))  // <tiles per wave, head tiles, hidden tiles per wave>
+          return std::snprintf(buf, cap, "%s<%d, %d, %d>", p.gru.cell == 1 ? "policy_lstm_kernel" : "policy_gru_kernel",
+                               TPW, HT, gt);
+      }
+      return std::snprintf(buf, cap, "policy_fused_kernel<4, %d, %d, %d, %d, %d, %d>", TPW, HT, C0M, RNN, ACTC, NHC);
+    }
   });
 }
 

@@ -16,6 +16,7 @@
 // (chunk, tile): packed[c][t][gate][lane].
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #define GO2PI_MAX_LAYERS 8
@@ -225,6 +226,13 @@ int launch_gemv_layer(const DevProgram &p, int layer, const float *x, int x_stri
                       int batch, void *stream);
 size_t gemv_lds_bytes(const DevProgram &p, int layer);
 int configure_kernels(const DevProgram &p, int waves);
+// The instantiation launch_policy_fused runs for one tick of fewer than 2^20 rows, as
+// "kernel<template arguments>", printed by the dispatch that launches it.
+int batched_kernel_name(const DevProgram &p, int waves, char *buf, size_t cap);
+// ... and the kernels of the batch <= GO2PI_SMALL_MAXB launches (launch_latency: its
+// general instantiations report the same name; launch_gemv_layer)
+const char *latency_kernel_name();
+const char *gemv_kernel_name();
 // batch <= GO2PI_SMALL_MAXB act() in one launch; gran: [nl-1][gstride] u64 granules
 // (tag = epoch0 + layer), err: host-visible word set to 1 on a hand-off timeout,
 // done: host-visible word set to epoch0 once the action is written (final layer
@@ -272,21 +280,32 @@ int launch_latency_ctl(const DevProgram &p, const DevProgram *p_dev, const DevCt
 // act() form: the action rows travel to the host as {epoch, value} granules in actg
 // (host-mapped [SMALL_MAXB][out_dim]): the host checks the data itself, so no drain
 // and no done word sit between the last store and the answer.
+// tiled0: layer 0 tiled over the workgroups even where its local form applies
+// (GO2PI_RES_TILED0 at engine creation, A/B diagnostics).
 int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned long long *req,
                     unsigned long long *actg,
                     unsigned long long *gran, int gstride, unsigned long long *mirror, unsigned *err,
                     unsigned *done, unsigned long long idle_ticks, const DevCtl *ctl, unsigned long long *hgran,
-                    float *hidden, const unsigned *yield, void *stream);
+                    float *hidden, const unsigned *yield, bool tiled0, void *stream);
 
-// The single-workgroup resident form (resident.hip policy_resident1_kernel, r04):
-// dense policies of <= 4 layers whose weights fit one CU's registers, at most 16
-// outputs. Same request / answer / leave protocol as launch_resident.
-bool resident1_fits(const DevProgram &p, bool ctl);  // ctl: the controller form (512 threads)
-// The controller form answers in granules too when policy_act1_kernel serves it (r05;
-// true here): actg holds ctl_gran(in_dim).total granules, each output value tagged with
-// the request's epoch, and there is no done word per request (the r04 forms and
-// launch_resident's drain the plain outputs into ctl's staging, then set done).
-bool resident1_ctl_granules(const DevProgram &p);
+// The resident kernel that serves one kind of request (act(), or the controller tick) of an
+// engine, decided once when the engine is created (engine.cpp build): resident_start
+// launches it, resident_serve reads its answer accordingly, go2pi_resident_kernel names it.
+//   Act1   policy_act1_kernel (r05): one workgroup, a polling wave; answers in granules,
+//          the controller form too (actg holds ctl_gran(in_dim).total granules, each output
+//          value tagged with the request's epoch, and there is no done word per request)
+//   R1     policy_resident1_kernel (r04): one workgroup; its controller form drains the
+//          plain outputs into ctl's staging, then sets done
+//   Wide   policy_wide_kernel (r06, resident_wide.hip): act() only
+//   Multi  policy_resident_kernel: one workgroup per tile; controller form as R1's
+enum class ResForm { None, Act1, R1, Wide, Multi };
+
+// The single-workgroup resident forms: dense policies of <= 4 layers whose weights fit one
+// CU's registers, at most 16 outputs. Same request / answer / leave protocol as launch_resident.
+bool resident_act1_fits(const DevProgram &p);       // Act1's shape (act1_shape(p).nl != 0)
+bool resident_r1_fits(const DevProgram &p, bool ctl);  // R1's registers; ctl: the controller form (512 threads)
+// form + "ring=..." as go2pi_resident_kernel reports it (Wide: with wide_shape's arguments)
+void resident_kernel_name(ResForm form, const DevProgram &p, bool ring_vram, char *buf, size_t cap);
 // Offsets (in granules) of the controller form's answer, fixed for GO2PI_SMALL_MAXB rows:
 // action [8][12], q_des / kp / kd [8][12][2] (each double's low then high 32 bits),
 // the new observation rows [8][in_dim], status [8]. Only the requested outputs are written.
@@ -297,10 +316,12 @@ constexpr CtlGran ctl_gran(int in_dim) {  // (constexpr: callable from device co
   constexpr int R = GO2PI_SMALL_MAXB, D = GO2PI_CTL_DOF;
   return CtlGran{0, R * D, 3 * R * D, 5 * R * D, 7 * R * D, 7 * R * D + R * in_dim, 7 * R * D + R * in_dim + R};
 }
-// ctl non-null: the controller-tick form (launch_resident's ctl semantics).
+// ctl non-null: the controller-tick form (launch_resident's ctl semantics). form: Act1 or
+// R1. Act1's act() form of the shipped shape: depth poll sweeps in flight (1, else 2) on cw
+// compute waves (4, else 8) (GO2PI_A1_DEPTH / GO2PI_A1_CW at engine creation, A/B).
 int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigned long long *req,
                      unsigned long long *actg, unsigned *err, unsigned *done, unsigned long long idle_ticks,
-                     const unsigned *yield, const DevCtl *ctl, void *stream);
+                     const unsigned *yield, const DevCtl *ctl, ResForm form, int depth, int cw, void *stream);
 
 // The resident act() for wide dense policies (resident_wide.hip policy_wide_kernel, r06):
 // 3..5 dense layers, every hidden layer H = 256 or 512 wide, a head of <= 16 outputs,
@@ -315,6 +336,7 @@ struct WideShape {
   int nl, cw, f0, pro;
 };
 WideShape wide_shape(const DevProgram &p);  // nl = 0: does not apply
+int wide_kernel_name(const DevProgram &p, char *buf, size_t cap);  // "policy_wide_kernel<nl, cw, f0, pro>"
 int launch_resident_wide(const DevProgram &p, const DevProgram *p_dev, const unsigned long long *req,
                          unsigned long long *actg, unsigned long long *gran, int gstride, unsigned *err, unsigned *done,
                          unsigned long long idle_ticks, const unsigned *yield, void *stream);

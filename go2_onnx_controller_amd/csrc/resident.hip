@@ -33,7 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
+#include <cstdio>
 
 #include "ctl_fn.hpp"
 #include "device_fn.hpp"
@@ -875,8 +875,9 @@ struct A1Shape {
 };
 A1Shape act1_shape(const DevProgram &p);
 
-bool resident1_fits(const DevProgram &p, bool ctl) {
-  if (act1_shape(p).nl && !std::getenv("GO2PI_RES_R1W")) return true;  // policy_act1_kernel (r05)
+bool resident_act1_fits(const DevProgram &p) { return act1_shape(p).nl != 0; }
+
+bool resident_r1_fits(const DevProgram &p, bool ctl) {
   const int nt = ctl ? 512 : 1024;
   // (nl >= 2: with one layer nothing would separate the request loop's top barrier from
   // the polling wave's next writes of st / x0)
@@ -889,8 +890,6 @@ bool resident1_fits(const DevProgram &p, bool ctl) {
   }
   return p.L[0].K_pad <= nt;
 }
-
-bool resident1_ctl_granules(const DevProgram &p) { return act1_shape(p).nl && !std::getenv("GO2PI_RES_R1W"); }
 
 // CTL: the controller tick (go2pi_controller_step at batch <= 8), as the multi-
 // workgroup kernel's controller form: the request carries the tick's raw rows
@@ -1675,11 +1674,13 @@ size_t resident1_lds_bytes(const DevProgram &p, bool ctl) {
 
 int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigned long long *req,
                      unsigned long long *actg, unsigned *err, unsigned *done, unsigned long long idle_ticks,
-                     const unsigned *yield, const DevCtl *ctl, void *stream) {
-  if (!resident1_fits(p, ctl != nullptr)) return (int)hipErrorInvalidValue;
+                     const unsigned *yield, const DevCtl *ctl, ResForm form, int depth, int cw, void *stream) {
+  const A1Shape a1 = act1_shape(p);
+  if (form == ResForm::Act1 ? !a1.nl : !(form == ResForm::R1 && resident_r1_fits(p, ctl != nullptr)))
+    return (int)hipErrorInvalidValue;
   // a LayerNormalization program: policy_act1_kernel's act() form only (LN = true)
   const bool ln = program_has_ln(p);
-  if (ln && (ctl || !resident1_ctl_granules(p))) return (int)hipErrorInvalidValue;
+  if (ln && (ctl || form != ResForm::Act1)) return (int)hipErrorInvalidValue;
   const size_t lds = resident1_lds_bytes(p, ctl != nullptr);  // (r04's forms)
   auto go = [&](auto kern, int nt) {
     if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
@@ -1696,11 +1697,9 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
   // instantiation: the registers it leaves free keep the controller form out of scratch
   // (Elu alpha 1 on the hidden layers, no activation on the head: the exported policy's)
   const bool elu1 = r1_acts(p) == 0x0111u && p.L[0].alpha == 1.f && p.L[1].alpha == 1.f && p.L[2].alpha == 1.f;
-  // r05: the polling-wave form (policy_act1_kernel) wherever its shape applies
-  // (GO2PI_RES_R1W=1: the r04 1024-thread form, A/B diagnostics; GO2PI_A1_DEPTH: poll
-  // sweeps in flight, 1 / 2 / 4)
-  const A1Shape a1 = act1_shape(p);
-  if (a1.nl && !std::getenv("GO2PI_RES_R1W")) {
+  // r05: the polling-wave form (policy_act1_kernel), which the engine picks wherever its
+  // shape applies (GO2PI_RES_R1W=1 at its creation: the r04 1024-thread form, A/B diagnostics)
+  if (form == ResForm::Act1) {
     // (the controller form: the assembly's image, layer 0's weights, lane-major, and the
     // new observation rows besides)
     const size_t lds1 = sizeof(float) * (3 * (size_t)GO2PI_SMALL_MAXB * p.lds_stride + 4 +
@@ -1725,11 +1724,7 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
                          ctl ? *ctl : DevCtl{});
       return (int)hipGetLastError();
     };
-    const char *dv = std::getenv("GO2PI_A1_DEPTH");
-    const int depth = dv ? std::atoi(dv) : 2;
     const bool pro = p.pre_sub || p.pre_div || p.pre_mul || p.pre_clip;
-    const char *cv = std::getenv("GO2PI_A1_CW");
-    const int cw = cv && std::atoi(cv) == 4 ? 4 : 8;
     if (ln) return a1_generic_ln(a1, go1);
     if (ctl) {  // the controller form: one sweep in flight (three loads per lane), eight compute waves
       if (a1.nl == 4 && a1.h == 128 && a1.f0 == 2 && elu1)
@@ -1737,7 +1732,7 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
       return a1_generic_ctl(a1, go1);
     }
     if (a1.nl == 4 && a1.h == 128 && a1.f0 == 2 && elu1 && !pro) {
-      if (cw == 8) {
+      if (cw != 4) {
         if (depth == 1) return go1(policy_act1_kernel<4, 128, 2, 0x0111u, 1, false, 8>, 8);
         return go1(policy_act1_kernel<4, 128, 2, 0x0111u, 2, false, 8>, 8);
       }
@@ -1762,7 +1757,7 @@ int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned
                     unsigned long long *actg,
                     unsigned long long *gran, int gstride, unsigned long long *mirror, unsigned *err,
                     unsigned *done, unsigned long long idle_ticks, const DevCtl *ctl, unsigned long long *hgran,
-                    float *hidden, const unsigned *yield, void *stream) {
+                    float *hidden, const unsigned *yield, bool tiled0, void *stream) {
   if (p.L[p.nl - 1].N_pad != 16) return (int)hipErrorInvalidValue;  // workgroup 0 owns the whole action
   for (int l = 0; l < p.nl; ++l)
     if (p.L[l].K_pad > RES_MAXS * RES_WAVES * 16) return (int)hipErrorInvalidValue;
@@ -1776,7 +1771,7 @@ int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned
   const int N0 = p.L[0].N_pad, C0 = p.L[0].K_pad >> 4;
   const int KS = (N0 > 0 && (RES_WAVES * 64) % N0 == 0) ? (RES_WAVES * 64) / N0 : 0;
   const int nf = KS > 0 ? 4 * ((C0 + KS - 1) / KS) : 0;
-  const bool local0 = !rnn && p.nl >= 2 && (nf == 8 || nf == 12 || nf == 16) && !std::getenv("GO2PI_RES_TILED0");
+  const bool local0 = !rnn && p.nl >= 2 && (nf == 8 || nf == 12 || nf == 16) && !tiled0;
   const int x0len = local0 ? (nf / 4) * KS * 16 : p.L[0].K_pad;
   // one workgroup per 16-output tile of the widest TILED layer (with a local layer 0,
   // workgroups beyond the later layers' tiles would only repeat layer 0 and poll)
@@ -1825,6 +1820,20 @@ int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned
   if (local0 && nf == 12) return go(policy_resident_kernel<12, false>);
   if (local0 && nf == 16) return go(policy_resident_kernel<16, false>);
   return go(policy_resident_kernel<0, false>);
+}
+
+void resident_kernel_name(ResForm form, const DevProgram &p, bool ring_vram, char *buf, size_t cap) {
+  const char *ring = ring_vram ? " ring=vram" : " ring=host";
+  char wide[64];
+  const char *k = "policy_resident_kernel";
+  switch (form) {
+    case ResForm::None: ring = "", k = "none"; break;
+    case ResForm::Act1: k = "policy_act1_kernel"; break;
+    case ResForm::R1: k = "policy_resident1_kernel"; break;
+    case ResForm::Wide: wide_kernel_name(p, wide, sizeof wide), k = wide; break;
+    case ResForm::Multi: break;
+  }
+  std::snprintf(buf, cap, "%s%s", k, ring);
 }
 
 }  // namespace go2pi

@@ -52,7 +52,7 @@
 // done = LEAVE after its own stores have drained (engine.cpp resident_serve).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
+#include <cstdio>
 
 #include "resident_fn.hpp"
 
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(64 * (1 + CW)) void policy_wide_kernel(const DevPro
 // {NL, CW, F0, PRO} of program p when policy_wide_kernel serves it, else NL = 0: a dense
 // policy of 3 or 4 layers whose hidden layers are all H = 256 or 512 wide, a head of
 // <= 16 outputs and layer 0 of K_pad <= 64 (<= 48 for 4 layers of 512). The one place
-// that decides the instantiation: launch_resident_wide runs it, go2pi_resident_kernel
+// that decides the instantiation: launch_resident_wide runs it, wide_kernel_name
 // names it.
 WideShape wide_shape(const DevProgram &p) {
   WideShape w{0, 0, 0, 0};
@@ -511,6 +511,11 @@ WideShape wide_shape(const DevProgram &p) {
   w.f0 = base ? 12 : 16;
   w.pro = (!base || p.pre_sub || p.pre_div || p.pre_mul || p.pre_clip) ? 1 : 0;
   return w;
+}
+
+int wide_kernel_name(const DevProgram &p, char *buf, size_t cap) {
+  const WideShape w = wide_shape(p);  // (what launch_resident_wide runs)
+  return std::snprintf(buf, cap, "policy_wide_kernel<%d, %d, %d, %d>", w.nl, w.cw, w.f0, w.pro);
 }
 
 size_t wide_lds_bytes(const WideShape &w) {

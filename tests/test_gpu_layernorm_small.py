@@ -169,7 +169,7 @@ def test_resident_default_form(tmp_path, name):
 ])
 def test_resident_other_forms(synth_path, name, env, monkeypatch):
     from go2_onnx_controller_amd import Engine
-    monkeypatch.setenv(env, "1")  # read at engine creation (GO2PI_A1_DEPTH: at each resident launch)
+    monkeypatch.setenv(env, "1")  # read at engine creation
     p = synth_path(name)
     with Engine(p, max_batch=8, ln_small=True, resident_ms=RES_MS) as e:
         kernel, ring = e.resident_kernel.split(" ring=")
@@ -185,7 +185,7 @@ def test_resident_other_forms(synth_path, name, env, monkeypatch):
 def test_resident_tiled0_bitwise_equals_single_launch(synth_path, name, monkeypatch):
     from go2_onnx_controller_amd import Engine
     monkeypatch.setenv("GO2PI_RES_MULTI", "1")   # read at engine creation
-    monkeypatch.setenv("GO2PI_RES_TILED0", "1")  # read at each resident launch
+    monkeypatch.setenv("GO2PI_RES_TILED0", "1")  # read at engine creation
     p = synth_path(name)
     with Engine(p, max_batch=8, ln_small=True, resident_ms=RES_MS) as r, Engine(p, max_batch=8, ln_small=True) as s:
         assert r.resident_kernel.startswith("policy_resident_kernel") and s.small_kernel == "policy_latency_kernel"

@@ -47,7 +47,7 @@ def test_resident_vs_launch_per_call(synth_path, name, form, monkeypatch):
     from oracle import mlp_ref
     tiled0 = form == "tiled0"
     if form == "one_d1":
-        monkeypatch.setenv("GO2PI_A1_DEPTH", "1")  # read at each resident launch
+        monkeypatch.setenv("GO2PI_A1_DEPTH", "1")  # read at engine creation, like every switch here
     elif form == "one_c4":
         monkeypatch.setenv("GO2PI_A1_CW", "4")  # four compute waves (one per SIMD)
     elif form == "one_r1w":
@@ -55,7 +55,7 @@ def test_resident_vs_launch_per_call(synth_path, name, form, monkeypatch):
     elif form not in ("one", "wide"):
         monkeypatch.setenv("GO2PI_RES_MULTI", "1")  # read at engine creation
     if tiled0:
-        monkeypatch.setenv("GO2PI_RES_TILED0", "1")  # read at each resident launch
+        monkeypatch.setenv("GO2PI_RES_TILED0", "1")  # read at engine creation
     path = _models(synth_path)[name]
     ref = mlp_ref.MlpRef.from_onnx(path)
     with Engine(path, max_batch=64, resident_ms=500) as r, Engine(path, max_batch=64) as p:
@@ -104,6 +104,29 @@ def test_resident_kernel_stays_live(synth_path, name, form, monkeypatch):
             if i % 20 == 0:
                 assert abs_err(y, ref.f64(x)) <= TOL, f"call {i} B={B}"
         assert e.resident_launches == 1, f"{e.resident_kernel}: {e.resident_launches} launches for 200 requests"
+
+
+@pytest.mark.parametrize("created_with,set_afterwards", [(None, "GO2PI_RES_R1W=1"), (None, "GO2PI_A1_DEPTH=1"),
+                                                          (None, "GO2PI_A1_CW=4"),
+                                                          ("GO2PI_RES_MULTI=1", "GO2PI_RES_TILED0=1")])
+def test_switch_after_creation_is_not_read(created_with, set_afterwards, monkeypatch):
+    """An engine's kernel choice is fixed when it is created: a diagnostic switch that
+    appears in the environment afterwards changes neither the kernel a relaunch runs nor
+    its answer. The batch-16 run in between stops the resident kernel (a batched launch),
+    so the second batch-1 request is served by a second resident launch."""
+    from go2_onnx_controller_amd import Engine
+    if created_with:
+        monkeypatch.setenv(*created_with.split("="))
+    with Engine(SHIPPED, max_batch=16, resident_ms=400) as e:
+        x = realistic_obs(1, seed=3)
+        first, kernel = e.run(x), e.resident_kernel
+        assert kernel != "none" and e.resident_launches == 1
+        monkeypatch.setenv(*set_afterwards.split("="))
+        e.run(realistic_obs(16, seed=4))
+        again = e.run(x)
+        assert np.array_equal(again, first), f"{set_afterwards} changed the answer of a live engine"
+        assert e.resident_kernel == kernel
+        assert e.resident_launches == 2
 
 
 def test_resident_known_answers():
