@@ -798,8 +798,10 @@ __device__ __forceinline__ float4 w4_epi(const ActP &ap, const f32x4 &acc, const
 // The lean kernel's Elu epilogue (ACTC == 1: Elu with alpha = 1, the exported
 // policies'): the bias is already in the accumulator (BIN: the first MFMA of each
 // tile took it as its C operand), and the x * log2(e) and e - 1 steps run as
-// packed pairs. Per element the value of act_t<1> with alpha = 1 (x > 0 ? x :
-// exp2(x * log2 e) - 1), the same bits for the same x (x = -0 aside, below).
+// packed pairs. Per element min(x, exp2(x * log2 e) - 1) by bit pattern (below):
+// the bits of act_t<1> with alpha = 1 for x >= 2^-10 (x itself) and wherever the
+// rounded e - 1 lies on the side of x the exact one does; for smaller |x| it can
+// differ from act_t<1> by up to one ulp of 1 (below).
 // (A select-free form, max(x, clamp(e, 0, 1) - 1), measured 0.4 % faster but maps
 // a NaN to -1 where ONNX Elu propagates it: rejected, DESIGN §4.1. The integer min
 // below propagates it.)
@@ -825,8 +827,13 @@ __device__ __forceinline__ float4 w4_epi_elu1(const f32x4 &acc, const float4 &bv
   // one v_min_i32 instead of a compare and a select): x > 0 (and +inf, and a NaN of
   // either sign) has e - 1 >= x with the same sign, so the smaller pattern is x; x <= 0
   // has x <= e - 1 <= 0, and negative patterns order by magnitude, so the min is e - 1
-  // (x = -inf: -1). Bitwise the compare + select's result except at x = -0, which
-  // gives -0 where the select gives +0.
+  // (x = -inf: -1). That ordering holds for the exact e - 1; the rounded one (e is
+  // within an ulp of 1 there) can fall on the other side of a tiny x: for 0 < x <
+  // 2^-10 (x^2 / 2 below the rounding of e) the min may return e - 1, which is 0 or
+  // up to one ulp of 1 away from x, and for tiny x < 0 it may return x where the
+  // select returns e - 1; x = -0 gives -0 where the select gives +0. Not the compare
+  // + select's bits, then, but within 2^-23 of them, and x >= 2^-10 returns x exactly:
+  // tests/test_gpu_probe_activations.py pins both per element (+-0, +-2^-100 ... +-3e-4).
   auto imin = [](float a, float b) {
     return __int_as_float(__builtin_elementwise_min(__float_as_int(a), __float_as_int(b)));
   };
