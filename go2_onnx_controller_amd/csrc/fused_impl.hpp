@@ -1426,6 +1426,13 @@ __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, 
     act_dispatch<ACTC>(hot.hid_act, [&](auto act_k) {
       constexpr int ACT = decltype(act_k)::value;
       float4 v[TPW];
+      // (T1: the epilogue stays behind the LDS phase as one block. Left free, the
+      // scheduler moves it up between that phase's last TPW MFMAs, which finish one
+      // tile each: a tile's VALU per MFMA gap, and every gap that holds VALU pays the
+      // fp32 MFMA's ~9-cycle switch on top of the instructions' own issue
+      // (tools/mfma_valu.hip: a packed Elu tile 91 cycles alone, 131 - 32 behind an
+      // MFMA). DESIGN §4.1 r10.)
+      if constexpr (T1) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < TPW; ++i) {
         if constexpr (ACTC == 1) v[i] = w4_epi_elu1<BIN>(acc[i], bv[i]);
@@ -1490,17 +1497,45 @@ __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, 
       for (int c = 0; c < NCH; ++c) hacc[h][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     act_dispatch<ACTC>(hot.hid_act, [&](auto act_k) {
       constexpr int ACT = decltype(act_k)::value;
+      if constexpr (T1) {
+        // the one-tick form: every tile's epilogue as one block behind the last LDS
+        // phase, then the head's MFMAs back to back behind ready operands (the same
+        // MFMAs in the same order on the same chains: the same bits). Interleaved per
+        // tile, each group of 4 MFMAs waited for its tile's v_exp results and every gap
+        // paid the MFMA / VALU switch (r10: 34.20 -> 33.78 us with the barrier above;
+        // without the barriers this order alone measured no gain).
+        float4 v[TPW];
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int i = 0; i < TPW; ++i) {
-        float4 v;
-        if constexpr (ACTC == 1) v = w4_epi_elu1<BIN>(acc[i], bv[i]);
-        else v = w4_epi<ACT>(ap, acc[i], bv[i]);
+        for (int i = 0; i < TPW; ++i) {
+          if constexpr (ACTC == 1) v[i] = w4_epi_elu1<BIN>(acc[i], bv[i]);
+          else v[i] = w4_epi<ACT>(ap, acc[i], bv[i]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int h = 0; h < HT; ++h) {
+        for (int i = 0; i < TPW; ++i) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            f32x4 &a = hacc[h][NCH == 4 ? j : (i & 1)];
-            a = mfma4(f4c(hw[h][i], j), f4c(v, j), a);
+          for (int h = 0; h < HT; ++h) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              f32x4 &a = hacc[h][NCH == 4 ? j : (i & 1)];
+              a = mfma4(f4c(hw[h][i], j), f4c(v[i], j), a);
+            }
+          }
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) {
+          float4 v;
+          if constexpr (ACTC == 1) v = w4_epi_elu1<BIN>(acc[i], bv[i]);
+          else v = w4_epi<ACT>(ap, acc[i], bv[i]);
+#pragma unroll
+          for (int h = 0; h < HT; ++h) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              f32x4 &a = hacc[h][NCH == 4 ? j : (i & 1)];
+              a = mfma4(f4c(hw[h][i], j), f4c(v, j), a);
+            }
           }
         }
       }
