@@ -851,10 +851,12 @@ __device__ __forceinline__ float4 w4_epi_elu1(const f32x4 &acc, const float4 &bv
 // past the layer's own chunks the ring loads NL's chunks (kbn + d) mod Cn, d < RD
 // (NL's consumption order), into the slots that follow: NL starts at slot
 // (K0S + C - k0) & 3, which must be the slot NL's own phase starts on.
-template <int TPW, int RD, int K0S, int NT, bool NEXT>
+// A0: chunk k0's B operand has been read already (*a0: the hand-off's early read, w4_step).
+template <int TPW, int RD, int K0S, int NT, bool NEXT, bool A0 = false>
 __device__ __forceinline__ void w4_lds_phase(const float *X, int xs, int lane, int C, int kb, int k0,
                                              const WStream &ws, int csb, const WStream &wn, int csn, int kbn, int Cn,
-                                             const int (&vo)[TPW], f32x4 (&acc)[TPW], float4 (&f)[4][TPW]) {
+                                             const int (&vo)[TPW], f32x4 (&acc)[TPW], float4 (&f)[4][TPW],
+                                             const float4 *a0 = nullptr) {
   static_assert(K0S >= 0 && K0S <= 3 && NT >= 1 && NT <= 4 && RD <= NT, "phase shape");
   const float *xrow = X + (lane & 15) * xs + ((lane >> 4) << 2);
   auto chunk_of = [&](int k) {
@@ -866,7 +868,8 @@ __device__ __forceinline__ void w4_lds_phase(const float *X, int xs, int lane, i
     return c >= Cn ? c - Cn : c;
   };
   float4 a[2];
-  a[0] = *reinterpret_cast<const float4 *>(xrow + chunk_of(k0) * 16);
+  if constexpr (A0) a[0] = *a0;
+  else a[0] = *reinterpret_cast<const float4 *>(xrow + chunk_of(k0) * 16);
   // one group of 4 chunks from k = g (slots K0S .. K0S + 3, mod 4); TAIL: the last
   auto group = [&](int g, auto tail_k) {
     constexpr bool TAIL = decltype(tail_k)::value;
@@ -1262,12 +1265,19 @@ __device__ __forceinline__ void w4_prefill(const float *l0w, float4 (&f)[4][TPW]
 // an activation). Its caller issued the ring's loads FIRST and the staging loads
 // after them, so the barrier below waits for every load; the head's tail is the
 // partial sums, the bias and the store.
-template <int TPW, int HT, bool CTL, bool PL, int C0M, int ACTC = -1, int NHC = 0, int NW = 4, bool T1 = false>
+// EHT: the early hand-off (r11), at 4 and 8 tiles per wave: the other
+// waves' flags are read before a layer's last own chunk and tested behind it, and the
+// head's fragments and bias come by buffer loads issued in front of the last hidden
+// layer's epilogue. The one-tick kernel and the lean GRU tick have it (measured on
+// mlp512 and GRU-256); every other kernel keeps the code below as it was.
+template <int TPW, int HT, bool CTL, bool PL, int C0M, int ACTC = -1, int NHC = 0, int NW = 4, bool T1 = false,
+          bool EHT = T1>
 __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, float *X0, float *Y0, int S,
                                         f32x4 *scratch, int *flags, float *lbias, int &ep, int wave, int lane,
                                         float *ac, const CtlView cv, int row0, int B, const DevCtl &ctl,
                                         const CtlLds &CL, int step, const float4 (&ring)[4][TPW], bool pre) {
   W4Hot hot = hot0;
+  constexpr bool HE = EHT && PL && !CTL && TPW >= 4;  // (with the register hand-off, HO below)
   constexpr int RD = GO2PI_W4_RD(TPW);
   constexpr int CH = NW * TPW;    // k-chunks of every layer after the first (= output tiles of a hidden layer)
   constexpr int CSB = CH * 1024;  // bytes per k-chunk of a hidden layer's (and layer 0's) fragments
@@ -1367,12 +1377,25 @@ __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, 
   // the head's fragments (final layer, fused): fetched before the last hidden layer's LDS phase
   float4 hw[HT][TPW];
   auto load_head = [&] {
-    load_bias<1>(hbv, hot.hb, wave < HT ? wave : 0, HT, lane);
-    const float4 *HW = reinterpret_cast<const float4 *>(hot.hw);
+    if constexpr (HE) {
+      // buffer loads, as the ring's: they count on vmcnt alone. (Loads through the
+      // program's generic pointers are flat loads, which count on lgkmcnt too: the last
+      // LDS phase's first B-operand read, an lgkmcnt(0) wait, waited for all nine of
+      // them to land.) The same addresses as below.
+      hbv[0] = WStream(hot.hb).ld(((wave < HT ? wave : 0) * 16 + ((lane >> 4) << 2)) * 4, 0);
+      const WStream wh(hot.hw);
 #pragma unroll
-    for (int h = 0; h < HT; ++h)
+      for (int h = 0; h < HT; ++h)
 #pragma unroll
-      for (int i = 0; i < TPW; ++i) hw[h][i] = HW[((size_t)(t0 + i) * HT + h) * 64 + lane];
+        for (int i = 0; i < TPW; ++i) hw[h][i] = wh.ld((((t0 + i) * HT + h) * 64 + lane) * 16, 0);
+    } else {
+      load_bias<1>(hbv, hot.hb, wave < HT ? wave : 0, HT, lane);
+      const float4 *HW = reinterpret_cast<const float4 *>(hot.hw);
+#pragma unroll
+      for (int h = 0; h < HT; ++h)
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) hw[h][i] = HW[((size_t)(t0 + i) * HT + h) * 64 + lane];
+    }
   };
   if (nh == 1) load_head();
   // layer 0: the observation tile, natural chunk order; the tail fetches layer 1's own chunks
@@ -1403,6 +1426,14 @@ __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, 
   for (int l = 1; l < nh; ++l) {
     const bool more = l + 1 < nh;
     const WStream ws(w4_layer_w<TPW, NW>(hot, l)), wn(w4_layer_w<TPW, NW>(hot, more ? l + 1 : l));
+    // (the early hand-off: the head's fragments go out in front of the last hidden layer's
+    // epilogue, so they land under it and its first own chunk. In front of the LDS phase,
+    // below, the phase's first MFMA waited for them: the compiler's wait there is
+    // vmcnt(0), it does not count nine newer loads off against the ring fragment it
+    // needs. r11: mlp512 33.72 -> 33.33 us.)
+    if constexpr (HE) {
+      if (!more) load_head();
+    }
     float4 bvn[TPW];
 #pragma unroll
     for (int i = 0; i < TPW; ++i) bvn[i] = *reinterpret_cast<const float4 *>(brow + l * CH * 16 + i * 16);
@@ -1419,6 +1450,9 @@ __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, 
     };
     // layer 1 sub-phases per wave: 28 + 3w + {own phase done, wait done, LDS phase done}
     [[maybe_unused]] const bool sub = lane == 0 && step == 0 && l == 1;
+    // the early hand-off (HE): whether the early flag read showed every epoch, the LDS phase's first B operand
+    [[maybe_unused]] bool hok = false;
+    [[maybe_unused]] float4 ha0 = {};
     {
     // own phase: layer l-1's epilogue for all the wave's tiles (to registers and LDS),
     // publish, then layer l's MFMAs over those chunks with the B operand from registers
@@ -1442,7 +1476,32 @@ __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, 
       for (int i = 0; i < TPW; ++i) *reinterpret_cast<float4 *>(yrow + i * 16) = v[i];
       GO2PI_STAMP(P, sub, 46 + wave);  // layer 1's epilogue issued (before the publish)
       constexpr bool LATEPUB = HO && PL;
-      if constexpr (LATEPUB) {
+      if constexpr (HE) {
+        // The early hand-off (r11): the other waves' flags are read before the last own
+        // chunk and tested behind its MFMAs, so the flag read's LDS round trip runs under
+        // that chunk instead of between the own phase's last MFMA and the LDS phase's
+        // first. The other waves published ~7K cycles earlier (after their first own
+        // chunk), so the test nearly always passes; if a flag is missing, w4_wait's loop
+        // below runs as before. Every lane reads a flag word (lane & (NW - 1); the wave's
+        // own word shows ep since its publish after chunk 0): no exec mask around the read.
+        static_assert((NW & (NW - 1)) == 0 && TPW >= 2 && LATEPUB, "flag word per lane, publish before the read");
+        [&]<int... I>(std::integer_sequence<int, I...>) {
+          ((w4_chunk<TPW, (I & 3), RD, true, true>(accn, f, v[I], ws, vo, ((t0 + I + RD) & (CH - 1)) * CSB),
+            I == 0 ? publish() : void()),
+           ...);
+        }(std::make_integer_sequence<int, TPW - 1>{});
+        constexpr int IL = TPW - 1;
+        __builtin_amdgcn_sched_barrier(0);
+        const int fl = __hip_atomic_load(flags + (lane & (NW - 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __builtin_amdgcn_sched_barrier(0);
+        w4_chunk<TPW, (IL & 3), RD, true, true>(accn, f, v[IL], ws, vo, ((t0 + IL + RD) & (CH - 1)) * CSB);
+        __builtin_amdgcn_sched_barrier(0);
+        hok = __ballot(fl < ep) == 0ull;
+        if (hok) {
+          asm volatile("" ::: "memory");  // the operand read stays behind the flag observation
+          ha0 = *reinterpret_cast<const float4 *>(Y + (lane & 15) * S + ((lane >> 4) << 2) + ((kb1 + TPW) & (CH - 1)) * 16);
+        }
+      } else if constexpr (LATEPUB) {
         // the lean kernel publishes after its first own chunk: the publish's
         // lgkmcnt(0) then finds the tile stores landed instead of holding the MFMAs
         // behind them (mlp512 35.55 -> 35.43 us median, profiles/r03_ab_latepub.json;
@@ -1463,16 +1522,37 @@ __device__ __forceinline__ void w4_step(const DevProgram &P, const W4Hot &hot0, 
     if constexpr (!HO) __syncthreads();
     }
     GO2PI_STAMP(P, sub, 28 + 3 * wave);
-    if constexpr (HO) w4_wait<NW>(flags, wave, ep, lane, hot.err);
-    GO2PI_STAMP(P, sub, 29 + 3 * wave);
     // LDS phase: the other waves' chunks, rotated order from t0 + TPW
     constexpr int K0 = HO ? TPW : 0;                             // first chunk index of the LDS phase
     constexpr int NT = (CH - K0) % 4 ? (CH - K0) % 4 : 4;       // chunks in the LDS phase's last group
+    if constexpr (HE) {
+      // WAR with the early read (the rule of the header comment holds): this wave writes
+      // layer l's tiles (the next round's epilogue, into the buffer layer l - 1 read)
+      // only behind this point, and it passes this point only after it has seen every
+      // wave's flag of this epoch, by the early read when hok, by w4_wait's loop
+      // otherwise; a wave sets that flag behind its own layer l - 1 contraction, its
+      // last read of that buffer. The early read moves the observation up, never the
+      // writes, and the first operand is read behind the observation on both paths.
+      if (!hok) {
+        w4_wait<NW>(flags, wave, ep, lane, hot.err);
+        ha0 = *reinterpret_cast<const float4 *>(Y + (lane & 15) * S + ((lane >> 4) << 2) + ((kb1 + K0) & (CH - 1)) * 16);
+      }
+      asm volatile("" ::: "memory");  // the LDS reads of the other waves' tiles stay behind the observation
+    } else if constexpr (HO) {
+      w4_wait<NW>(flags, wave, ep, lane, hot.err);
+    }
+    GO2PI_STAMP(P, sub, 29 + 3 * wave);
     if (more) {
-      w4_lds_phase<TPW, RD, (K0 & 3), NT, true>(Y, S, lane, CH, kb1, K0, ws, CSB, wn, CSB, kb1, CH, vo, accn, f);
+      if constexpr (HE)
+        w4_lds_phase<TPW, RD, (K0 & 3), NT, true, true>(Y, S, lane, CH, kb1, K0, ws, CSB, wn, CSB, kb1, CH, vo, accn, f, &ha0);
+      else
+        w4_lds_phase<TPW, RD, (K0 & 3), NT, true>(Y, S, lane, CH, kb1, K0, ws, CSB, wn, CSB, kb1, CH, vo, accn, f);
     } else {
-      load_head();  // the head's fragments, behind the last LDS phase
-      w4_lds_phase<TPW, RD, (K0 & 3), NT, false>(Y, S, lane, CH, kb1, K0, ws, CSB, wn, CSB, 0, 1, vo, accn, f);
+      if constexpr (!HE) load_head();  // the head's fragments, behind the last LDS phase
+      if constexpr (HE)
+        w4_lds_phase<TPW, RD, (K0 & 3), NT, false, true>(Y, S, lane, CH, kb1, K0, ws, CSB, wn, CSB, 0, 1, vo, accn, f, &ha0);
+      else
+        w4_lds_phase<TPW, RD, (K0 & 3), NT, false>(Y, S, lane, CH, kb1, K0, ws, CSB, wn, CSB, 0, 1, vo, accn, f);
     }
     GO2PI_STAMP(P, sub, 30 + 3 * wave);
 #pragma unroll
@@ -1920,8 +2000,10 @@ __device__ __forceinline__ void w4_gru_body(const DevProgram &P, const float *ob
     float *hl = bufH + (lane & 15) * S + wave * GT * 16 + ((lane >> 4) << 2);
 #pragma unroll
     for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hl + i * 16) = hn[i];
-    w4_step<TPW, HT, false, true, 0, 1, 3>(P, hot, bufB, bufA, S, scratch, flags, lbias, ep, wave, lane, act,
-                                           CtlView{}, row0, B, DevCtl{}, CtlLds{}, step, ring0, true);
+    // (the early hand-off in the GRU tick, where it was measured: GRU-256 55.9 -> 55.6 us per
+    // tick, 5278 -> 5269 us per 100-tick launch; the LSTM tick keeps the parent's code)
+    w4_step<TPW, HT, false, true, 0, 1, 3, 4, false, (!LSTM && TPW >= 4)>(P, hot, bufB, bufA, S, scratch, flags, lbias, ep, wave, lane,
+                                                            act, CtlView{}, row0, B, DevCtl{}, CtlLds{}, step, ring0, true);
   }
   GO2PI_STAMP(P, tid == 0, 2);
   GO2PI_STAMP_RT(P, tid == 0, 3);
