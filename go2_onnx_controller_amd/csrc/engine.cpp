@@ -4,7 +4,7 @@
 // (onnx_inference/src/cpp/onnx_actor.cpp:6-48) with an MI355X-native runtime:
 //  - load: parse the .onnx with our own reader (onnx_model.cpp), lower it to a
 //    program of dense layers (+ optional GRU), pack weights once into MFMA
-//    fragment order (program.hpp) and upload them to HBM (one arena);
+//    fragment order (plan.cpp, program.hpp) and upload them to HBM (one arena);
 //  - host path (go2pi_run): small batches replay a captured hipGraph whose
 //    kernels read the observation from / write the action to pinned,
 //    host-mapped staging (no memcpy nodes); larger batches stage through
@@ -16,7 +16,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,52 +33,16 @@
 
 #include "../../include/go2pi.h"
 #include "onnx_model.hpp"
+#include "plan.hpp"
 #include "program.hpp"
 
 namespace {
 
+using go2pi::ApiError;
 using go2pi::ResForm;
+using go2pi::Switches;
 
 thread_local std::string g_last_error;
-
-// The process's diagnostic switches (GO2PI_* environment variables; DESIGN §4.5 lists
-// them), read once per engine at the top of build(): every choice an engine makes from
-// them is made there and holds for its life. Except where noted a switch is on when the
-// variable is set, to any value.
-struct Switches {
-  bool req_host;               // REQ_HOST: the request ring in pinned host memory (bar_take)
-  bool no_head_fuse, no_w4;    // NO_HEAD_FUSE: no head fusion, and so no 4-wave pipeline; NO_W4: no pipeline
-  bool k0_pad64;               // K0_PAD64: the pipeline's layer 0 padded to 64 columns, not 16
-  bool small_chain;            // SMALL_CHAIN: batch <= 8 by the GEMV chain (no single launch, no resident form)
-  unsigned epoch0;             // EPOCH0=<u32>: the first granule tag instead of 1; 0 (unset, out of range): ignored
-  bool diag_stamps;            // DIAG_STAMPS: per-workgroup clock stamps
-  bool no_plain;               // NO_PLAIN: the general pipeline body, not the lean kernel
-  bool lean_rt_act, lean_rt_nh;  // LEAN_RT_ACT / _NH: the lean kernel's activation / layer count read at run time
-  // GRU_GENERAL: the general body, not the lean recurrent tick (r05 same-box A/B, GRU-256 at
-  // 4096 robots: 56.7 against 60.5-60.9 us per one-tick launch); CTL_GENERAL: ... not the lean controller tick
-  bool gru_general, ctl_general;
-  bool res_multi;              // RES_MULTI: the multi-workgroup resident kernel for every form
-  bool res_r1w;                // RES_R1W: never policy_act1_kernel (r04's policy_resident1_kernel where it fits)
-  bool res_tiled0;             // RES_TILED0: the multi-workgroup kernel's layer 0 tiled, not local
-  int a1_depth, a1_cw;         // A1_DEPTH: policy_act1_kernel's poll sweeps in flight, 1 for the value 1, else 2;
-                               // A1_CW: its compute waves, 4 for the value 4, else 8
-
-  static Switches read() {
-    auto env = [](const char *name) { return std::getenv(name); };  // (the engine's only look at the environment)
-    auto on = [&](const char *name) { return env(name) != nullptr; };
-    auto num = [&](const char *name) { return env(name) ? std::atoi(env(name)) : 0; };
-    const unsigned long long e0 = env("GO2PI_EPOCH0") ? std::strtoull(env("GO2PI_EPOCH0"), nullptr, 0) : 0ull;
-    return Switches{.req_host = on("GO2PI_REQ_HOST"), .no_head_fuse = on("GO2PI_NO_HEAD_FUSE"),
-                    .no_w4 = on("GO2PI_NO_W4"), .k0_pad64 = on("GO2PI_K0_PAD64"),
-                    .small_chain = on("GO2PI_SMALL_CHAIN"), .epoch0 = e0 <= 0xFFFFFFFFull ? (unsigned)e0 : 0u,
-                    .diag_stamps = on("GO2PI_DIAG_STAMPS"), .no_plain = on("GO2PI_NO_PLAIN"),
-                    .lean_rt_act = on("GO2PI_LEAN_RT_ACT"), .lean_rt_nh = on("GO2PI_LEAN_RT_NH"),
-                    .gru_general = on("GO2PI_GRU_GENERAL"), .ctl_general = on("GO2PI_CTL_GENERAL"),
-                    .res_multi = on("GO2PI_RES_MULTI"), .res_r1w = on("GO2PI_RES_R1W"),
-                    .res_tiled0 = on("GO2PI_RES_TILED0"), .a1_depth = num("GO2PI_A1_DEPTH") == 1 ? 1 : 2,
-                    .a1_cw = num("GO2PI_A1_CW") == 4 ? 4 : 8};
-  }
-};
 
 // Spin with the host's pause cadence until done() holds; the clock is read every 1024
 // turns and the wait gives up after 2 s. Returns done()'s last word.
@@ -102,14 +65,6 @@ void hip_check(hipError_t e, const char *what) {
   if (e != hipSuccess) throw HipError(std::string("HIP error in ") + what + ": " + hipGetErrorString(e), GO2PI_E_DEVICE);
 }
 void hip_check(int e, const char *what) { hip_check(static_cast<hipError_t>(e), what); }
-
-struct ApiError : std::runtime_error {
-  int code;
-  ApiError(const std::string &m, int c) : std::runtime_error(m), code(c) {}
-};
-
-inline int ceil16(int x) { return (x + 15) & ~15; }
-inline int ceil64(int x) { return (x + 63) & ~63; }
 
 // Pinned host-mapped blocks are never returned to HIP while the process runs:
 // hipHostFree (like hipFree) performs an implicit hipDeviceSynchronize, which
@@ -252,7 +207,7 @@ std::mutex g_res_mu;
 struct go2pi_engine {
   go2pi::Model model;
   go2pi_opts opts{};
-  Switches sw{};  // as the environment stood when build() began
+  Switches sw{};  // as the environment stood when build() began (plan.hpp)
   int device = 0;
   int waves = 8;
   int small_batch = 8;
@@ -287,7 +242,7 @@ struct go2pi_engine {
   bool resident_ok = false, resident_live = false;
   std::atomic<int> res_flag{0};  // resident_live, readable from other threads (evict_residents)
   // the kernel that serves act() and the one that serves a controller tick (program.hpp
-  // ResForm), decided in build(); res_ctl None: ticks are served by a launch each (the
+  // ResForm), decided by the planner (plan.cpp plan_resident); res_ctl None: ticks are served by a launch each (the
   // controller form applies to dense policies without LayerNormalization)
   ResForm res_act = ResForm::None, res_ctl = ResForm::None;
   unsigned long long *d_hgran = nullptr;  // GRU form: [2][SMALL_MAXB][H] hidden-row granules (two buffers)
@@ -752,51 +707,6 @@ std::unique_lock<std::mutex> evict_residents(const go2pi_engine *self, int64_t b
   return lk;
 }
 
-// K is padded to a multiple of 64 (4 chunks: the kernel's unroll); a hidden layer's
-// N to its consumer's K_pad (64), the final layer's N to 16 (one MFMA tile).
-void pack_dense(const go2pi::Dense &d, bool last, std::vector<float> &w, std::vector<float> &b, int &K_pad,
-                int &N_pad, int kq = 64) {
-  K_pad = kq == 16 ? ceil16(d.K) : ceil64(d.K);
-  N_pad = last ? ceil16(d.N) : ceil64(d.N);
-  const int T = N_pad / 16, C = K_pad / 16;
-  w.assign((size_t)T * C * 64 * 4, 0.f);
-  for (int t = 0; t < T; ++t)
-    for (int c = 0; c < C; ++c)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 4; ++j) {
-          const int n = 16 * t + (lane & 15), k = 16 * c + 4 * (lane >> 4) + j;
-          w[(((size_t)c * T + t) * 64 + lane) * 4 + j] = (n < d.N && k < d.K) ? d.W[(size_t)n * d.K + k] : 0.f;
-        }
-  b.assign(N_pad, 0.f);
-  std::copy(d.b.begin(), d.b.end(), b.begin());
-}
-
-// Recurrent-cell fragments: [Cx + Ch][Ht][gate][lane] float4 over the concatenated
-// [x (I_pad) | h (H)] axis; x chunks carry W, h chunks carry R. G = 3 gates (GRU:
-// z, r, h) or 4 (LSTM: i, o, f, c), in ONNX row order.
-void pack_gru(const go2pi::Gru &g, std::vector<float> &w, int &I_pad) {
-  I_pad = ceil64(g.I);  // whole 4-chunk groups of x (the pipelined cell's ring runs on them)
-  const int H = g.H, Ht = H / 16, Cx = I_pad / 16, Ch = H / 16, Cc = Cx + Ch, G = g.G;
-  w.assign((size_t)Ht * Cc * G * 64 * 4, 0.f);
-  for (int t = 0; t < Ht; ++t)
-    for (int c = 0; c < Cc; ++c)
-      for (int gate = 0; gate < G; ++gate)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 4; ++j) {
-            const int unit = 16 * t + (lane & 15);
-            const int row = gate * H + unit;
-            float v = 0.f;
-            if (c < Cx) {
-              const int k = 16 * c + 4 * (lane >> 4) + j;
-              if (k < g.I) v = g.W[(size_t)row * g.I + k];
-            } else {
-              const int k = 16 * (c - Cx) + 4 * (lane >> 4) + j;
-              v = g.R[(size_t)row * H + k];
-            }
-            w[((((size_t)c * Ht + t) * G + gate) * 64 + lane) * 4 + j] = v;
-          }
-}
-
 void set_ctl_params(go2pi_engine &e, const go2pi_ctl_params &cp) {
   go2pi::DevCtlParams d{};
   for (int i = 0; i < GO2PI_CTL_DOF; ++i) d.q0[i] = cp.q0[i];
@@ -811,40 +721,8 @@ void set_ctl_params(go2pi_engine &e, const go2pi_ctl_params &cp) {
   hip_check(hipMemcpy(e.d_ctl, &d, sizeof(d), hipMemcpyHostToDevice), "hipMemcpy");
 }
 
-// A policy with a LayerNormalization on any layer: served by the general batched body
-// and the GEMV chain only (no pipeline / lean kernel, latency kernel or resident form);
-// with opts.ln_small = 1 a dense one also by the latency kernel and, of the resident
-// forms, policy_act1_kernel's act() form or the multi-workgroup kernel (ln_small_on).
-bool has_ln(const go2pi::Model &m) {
-  for (const auto &d : m.layers)
-    if (d.ln) return true;
-  return false;
-}
-
-// The 4-wave uniform-MLP pipeline (fused_impl.hpp w4_step) applies to a policy
-// whose hidden layers are all 64 * TPW wide (TPW = 2, 4 or 8) with one
-// activation, and whose final layer is at most 2 tiles wide (1 at TPW = 8); a GRU
-// in front needs H % 64 == 0. It is the default (waves = 0) wherever it applies:
-// measured faster than the generic 8-wave body.
-bool w4_eligible(const go2pi_engine &e, const go2pi::Model &m) {
-  const int nl = (int)m.layers.size();
-  if (!(e.opts.waves == 0 || e.opts.waves == 4) || nl < 2) return false;
-  if (m.has_gru && m.gru.H % 64) return false;
-  if (m.has_gru && m.gru.cell == 0 && m.gru.lbr == 0) return false;  // the two-pass cell: generic body only
-  if (e.sw.no_head_fuse || e.sw.no_w4) return false;  // A/B diagnostics only
-  if (has_ln(m)) return false;  // LayerNormalization: the general body only (fused_impl.hpp ln_tile)
-  const int tpw = ceil64(m.layers[0].N) / 64, t_last = ceil16(m.layers[nl - 1].N) / 16;
-  if (!(tpw == 2 || tpw == 4 || tpw == 8) || t_last > (tpw == 8 ? 1 : 2)) return false;
-  for (int l = 0; l + 1 < nl; ++l)
-    if (ceil64(m.layers[l].N) != 64 * tpw || m.layers[l].act != m.layers[0].act ||
-        m.layers[l].alpha != m.layers[0].alpha || m.layers[l].beta != m.layers[0].beta)
-      return false;
-  return true;
-}
-
-// opts.ln_small: exactly 1 turns it on (the field fills the earlier layout's tail padding)
-bool ln_small_on(const go2pi_engine &e) { return e.opts.ln_small == 1; }
-
+// Engine creation, the straight-line part: every choice is the planner's (plan.cpp); here
+// its buffers are uploaded and what it says is allocated.
 void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o) {
   const Switches &sw = e.sw = Switches::read();
   go2pi_default_opts(&e.opts);
@@ -862,16 +740,8 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   } catch (const std::exception &ex) {
     throw ApiError(ex.what(), GO2PI_E_MODEL);
   }
-  auto &m = e.model;
-  if ((int)m.layers.size() > GO2PI_MAX_LAYERS)
-    throw ApiError("policy has more than " + std::to_string(GO2PI_MAX_LAYERS) + " dense layers", GO2PI_E_MODEL);
-  if (m.has_gru) {
-    // lbr = 0 (Keras reset_after=False) runs the generic body's two-pass cell
-    // (fused_impl.hpp gru0_cell), one tile group per wave: H <= 256
-    if (m.gru.cell == 0 && m.gru.lbr == 0 && m.gru.H > 256)
-      throw ApiError("GRU linear_before_reset=0 with hidden size > 256 is not supported", GO2PI_E_MODEL);
-    if (m.gru.H % 16) throw ApiError("recurrent hidden size must be a multiple of 16", GO2PI_E_MODEL);
-  }
+  const auto &m = e.model;
+  go2pi::check_model(m);
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -882,259 +752,78 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   hip_check(hipSetDevice(e.device), "hipSetDevice");
   hip_check(hipStreamCreateWithFlags(&e.stream, hipStreamNonBlocking), "hipStreamCreate");
 
-  // 8 waves per 16-robot workgroup (2 per SIMD) measured fastest with the
-  // interleaved schedule (kernels.hip, dense_acc note): 104K vs 106K cycles at 16
-  e.waves = (e.opts.waves == 4 || e.opts.waves == 16) ? e.opts.waves : 8;
-  e.small_batch = e.opts.small_batch == 0 ? GO2PI_SMALL_MAXB : std::min<int>(e.opts.small_batch, GO2PI_SMALL_MAXB);
+  const go2pi::Plan plan = go2pi::plan_program(m, e.opts, sw);
+  const go2pi::HostBuffers &buf = plan.buf;
+  go2pi::DevProgram &p = e.prog = plan.prog;
+  e.waves = plan.waves;
+  e.small_batch = plan.small_batch;
+  const int maxw = e.tmp_stride = plan.tmp_stride;
+  e.latency_ok = plan.latency_ok;
+  e.done_ok = plan.done_ok;
+  e.ctl_hist = plan.ctl_hist;
+  e.cost = plan.cost;
 
-  go2pi::DevProgram &p = e.prog;
-  std::memset(&p, 0, sizeof(p));
-  p.nl = (int)m.layers.size();
-  p.in_dim = m.in_dim;
-  p.out_dim = m.out_dim;
-  int maxw = 0;
-  double flops = 0, wbytes = 0;
-  // The 4-wave pipeline (decided below) takes a layer 0 of 3 (mod 4) k-chunks:
-  // a 48- or 98-wide observation is padded to 16 columns, not 64 (25 % / 12.5 %
-  // fewer layer-0 MFMAs and fragment bytes). Other kernels take any chunk count.
-  const bool w4_shape = w4_eligible(e, m);
-  const int k0q = (w4_shape && !m.has_gru && (ceil16(m.layers[0].K) / 16) % 4 == 3 && !sw.k0_pad64)
-                      ? 16 : 64;  // (the switch: A/B diagnostics only)
-  // every dense layer's fragments back to back in one arena (the pipeline finds
-  // layer l from the base: fused_impl.hpp w4_layer_w)
-  std::vector<std::vector<float>> packed(p.nl);
-  size_t arena = 0;
-  std::vector<size_t> off(p.nl);
+  // the plan's buffers to device memory, the program's pointers to them (empty: null)
+  auto opt_upload = [&](const std::vector<float> &v) { return v.empty() ? nullptr : e.upload(v); };
   for (int l = 0; l < p.nl; ++l) {
-    std::vector<float> b;
-    int kp, np;
-    pack_dense(m.layers[l], l == p.nl - 1, packed[l], b, kp, np, l == 0 ? k0q : 64);
-    off[l] = arena;
-    arena += packed[l].size();
-    auto &L = p.L[l];
-    L.bias = e.upload(b);
-    L.K_pad = kp;
-    L.N_pad = np;
-    L.N = m.layers[l].N;
-    L.act = m.layers[l].act;
-    L.alpha = m.layers[l].alpha;
-    L.beta = m.layers[l].beta;
-    if (const auto &d = m.layers[l]; d.ln) {
-      // scale and bias padded to N_pad with zeros; a pre-LN layer's dense store writes
-      // the raw pre-activation and the LN pass applies the layer's activation
-      std::vector<float> g(np, 0.f), bb(np, 0.f);
-      std::copy(d.ln_g.begin(), d.ln_g.end(), g.begin());
-      std::copy(d.ln_b.begin(), d.ln_b.end(), bb.begin());
-      L.ln = d.ln;
-      L.ln_eps = d.ln_eps;
-      L.ln_g = e.upload(g);
-      L.ln_b = e.upload(bb);
-      if (d.ln == 1) {
-        L.ln_act = L.act;
-        L.ln_alpha = L.alpha;
-        L.ln_beta = L.beta;
-        L.act = go2pi::ACT_NONE;
-        L.alpha = L.beta = 0.f;
-      }
-      wbytes += 4.0 * 2.0 * d.N;
-    }
-    maxw = std::max({maxw, kp, np});
-    flops += 2.0 * m.layers[l].K * m.layers[l].N;
-    wbytes += 4.0 * ((double)m.layers[l].K * m.layers[l].N + m.layers[l].N);
+    p.L[l].bias = e.upload(buf.bias[l]);
+    p.L[l].ln_g = opt_upload(buf.ln_g[l]);
+    p.L[l].ln_b = opt_upload(buf.ln_b[l]);
   }
-  {
-    std::vector<float> all;
-    all.reserve(arena);
-    for (auto &v : packed) all.insert(all.end(), v.begin(), v.end());
-    const float *base = e.upload(all);
-    for (int l = 0; l < p.nl; ++l) p.L[l].w = base + off[l];
+  const float *base = e.upload(buf.arena);
+  for (int l = 0; l < p.nl; ++l) p.L[l].w = base + buf.off[l];
+  if (p.has_gru) {
+    p.gru.w = e.upload(buf.gru_w);
+    p.gru.bzr = e.upload(buf.gru_bzr);
+    p.gru.bh = e.upload(buf.gru_bh);
+    const size_t nh = (size_t)e.opts.max_batch * p.gru.sw;
+    e.d_hidden = e.dalloc<float>(nh);
+    hip_check(hipMemsetAsync(e.d_hidden, 0, nh * sizeof(float), e.stream), "hipMemsetAsync");
   }
-  if (m.has_gru) {
-    std::vector<float> w;
-    int ip;
-    pack_gru(m.gru, w, ip);
-    const int H = m.gru.H, G = m.gru.G;
-    std::vector<float> bzr(2 * H), bh(2 * H);
-    if (m.gru.cell == 1) {  // LSTM: every gate's two biases summed (i, o, f, c)
-      bzr.resize(4 * H);
-      for (int j = 0; j < 4 * H; ++j) bzr[j] = m.gru.Wb[j] + m.gru.Rb[j];
-    } else {
-      for (int j = 0; j < H; ++j) {
-        bzr[j] = m.gru.Wb[j] + m.gru.Rb[j];
-        bzr[H + j] = m.gru.Wb[H + j] + m.gru.Rb[H + j];
-        bh[j] = m.gru.Wb[2 * H + j];
-        bh[H + j] = m.gru.Rb[2 * H + j];
-      }
-    }
-    p.has_gru = 1;
-    p.gru.w = e.upload(w);
-    p.gru.bzr = e.upload(bzr);
-    p.gru.bh = e.upload(bh);
-    p.gru.I = m.gru.I;
-    p.gru.I_pad = ip;
-    p.gru.H = H;
-    p.gru.lbr = m.gru.lbr;
-    p.gru.cell = m.gru.cell;
-    p.gru.sw = m.gru.cell == 1 ? 2 * H : H;
-    p.in_pad = ip;
-    maxw = std::max({maxw, ip, H});
-    flops += 2.0 * G * H * ((double)m.gru.I + H);
-    wbytes += 4.0 * ((double)G * H * (m.gru.I + H) + 2.0 * G * H);
-    const size_t sw = (size_t)p.gru.sw;
-    e.d_hidden = e.dalloc<float>((size_t)e.opts.max_batch * sw);
-    hip_check(hipMemsetAsync(e.d_hidden, 0, (size_t)e.opts.max_batch * sw * sizeof(float), e.stream), "hipMemsetAsync");
-  } else {
-    p.in_pad = p.L[0].K_pad;
-  }
-  p.lds_stride = maxw + 4;  // +16 B per row: rows start on different LDS banks
-  // Every LDS column a layer reads is written first (hidden N_pad == next K_pad,
-  // the observation stage writes [0, in_pad)), except after a GRU whose H is not
-  // a multiple of 64: then the columns [H, ceil64(H)) must be cleared once.
-  p.zero_fill = (m.has_gru && m.gru.H % 64) ? 1 : 0;
-  // head fusion: a narrow final layer (<= 2 tiles) whose predecessor runs one tile
-  // group set per wave (T >= waves) is folded into the predecessor's epilogue
-  if (p.nl >= 2 && !sw.no_head_fuse) {  // (the switch: A/B diagnostics only)
-    const int t_last = p.L[p.nl - 1].N_pad / 16, t_prev = p.L[p.nl - 2].N_pad / 16;
-    // (not behind a LayerNormalization: dense_layer_head feeds the head from un-normalised registers)
-    if (t_last <= 2 && t_prev >= e.waves && !p.L[p.nl - 2].ln) p.head_fuse = t_last;
-  }
-  // 4-wave uniform-MLP pipeline (kernels.hip, w4_step): a fused head, and
-  // every hidden layer exactly one group of 2, 4 or 8 tiles per wave. It is the
-  // default (waves = 0) wherever it applies: measured faster than the generic
-  // 8-wave body; otherwise waves = 0 means 8.
-  // (a GRU policy runs its cell first and hands h' to the pipeline as layer 0's input)
-  if (w4_shape) {
-    const int t_last = p.L[p.nl - 1].N_pad / 16;
-    const int tpw = p.L[0].N_pad / 64;
-    {
-      e.waves = 4;
-      p.head_fuse = t_last;
-      p.w4_tpw = tpw;
-      p.w4_bias = (p.nl - 1) * 64 * tpw;
-      std::vector<float> pack(p.w4_bias);
-      for (int l = 0; l + 1 < p.nl; ++l)
-        hip_check(hipMemcpy(pack.data() + (size_t)l * 64 * tpw, p.L[l].bias, sizeof(float) * 64 * tpw,
-                            hipMemcpyDeviceToHost),
-                  "hipMemcpy");
-      p.w4_bpack = e.upload(pack);
-    }
-  }
-
-  // prologue: model-defined (Sub/Div/Mul/Clip nodes) and/or opts-defined normalisation
-  std::vector<float> sub = m.pre_sub, div = m.pre_div;
-  if (e.opts.obs_mean) {
-    if (!sub.empty()) throw ApiError("model already normalises its input; obs_mean not allowed", GO2PI_E_INVALID);
-    sub.assign(e.opts.obs_mean, e.opts.obs_mean + m.in_dim);
-  }
-  if (e.opts.obs_std) {
-    if (!div.empty()) throw ApiError("model already normalises its input; obs_std not allowed", GO2PI_E_INVALID);
-    div.assign(e.opts.obs_std, e.opts.obs_std + m.in_dim);
-  }
-  if (!sub.empty()) { p.pre_sub = e.upload(sub); p.pre_sub_bcast = sub.size() == 1; }
-  if (!div.empty()) { p.pre_div = e.upload(div); p.pre_div_bcast = div.size() == 1; }
-  if (!m.pre_mul.empty()) {
-    if (e.opts.obs_mean || e.opts.obs_std)
-      throw ApiError("model already scales its input; obs_mean / obs_std not allowed", GO2PI_E_INVALID);
-    p.pre_mul = e.upload(m.pre_mul);
-    p.pre_mul_bcast = m.pre_mul.size() == 1;
-  }
-  p.obs_lo = m.pre_lo;
-  p.obs_hi = m.pre_hi;
-  if (e.opts.obs_clip > 0.f) {
-    p.obs_lo = std::max(p.obs_lo, -e.opts.obs_clip);
-    p.obs_hi = std::min(p.obs_hi, e.opts.obs_clip);
-  }
-  p.pre_clip = (std::isfinite(p.obs_lo) || std::isfinite(p.obs_hi)) ? 1 : 0;
-  // action epilogue: the graph's trailing Clip / scalar Mul (post_fn: clip, then
-  // scale), then the options'. The options apply after the graph, which post_fn's
-  // fixed order tanh -> clip -> scale can only express when the graph adds no scale
-  // (and, for tanh, no clip either).
-  const bool m_clip = std::isfinite(m.clip_lo) || std::isfinite(m.clip_hi);
-  if (e.opts.action_tanh && (m_clip || m.post_scale != 1.f))
-    throw ApiError("action_tanh on a graph that clips or scales its output is not supported", GO2PI_E_INVALID);
-  if (e.opts.action_clip > 0.f && m.post_scale != 1.f)
-    throw ApiError("action_clip on a graph that scales its output is not supported", GO2PI_E_INVALID);
-  p.post_tanh = e.opts.action_tanh ? 1 : 0;
-  p.clip_lo = m.clip_lo;
-  p.clip_hi = m.clip_hi;
-  if (e.opts.action_clip > 0.f) {
-    p.clip_lo = std::max(p.clip_lo, -e.opts.action_clip);
-    p.clip_hi = std::min(p.clip_hi, e.opts.action_clip);
-  }
-  p.scale = m.post_scale * ((e.opts.action_scale != 0.f) ? e.opts.action_scale : 1.f);
-
-  const size_t lds = go2pi::fused_lds_bytes(p, e.waves);
-  if (lds > 160 * 1024)
-    throw ApiError("layer width " + std::to_string(maxw) + " needs " + std::to_string(lds) +
-                   " B of LDS per tile (> 160 KiB)", GO2PI_E_MODEL);
+  p.w4_bpack = opt_upload(buf.bpack);
+  p.pre_sub = opt_upload(buf.pre_sub);
+  p.pre_div = opt_upload(buf.pre_div);
+  p.pre_mul = opt_upload(buf.pre_mul);
 
   // buffers
   e.d_obs = e.dalloc<float>((size_t)e.opts.max_batch * m.in_dim);
   e.d_act = e.dalloc<float>((size_t)e.opts.max_batch * m.out_dim);
-  e.tmp_stride = maxw;
   e.d_tmp[0] = e.dalloc<float>((size_t)GO2PI_SMALL_MAXB * maxw);
   e.d_tmp[1] = e.dalloc<float>((size_t)GO2PI_SMALL_MAXB * maxw);
   e.palloc(&e.h_obs, &e.m_obs, sizeof(float) * GO2PI_SMALL_MAXB * m.in_dim);
   e.palloc(&e.h_act, &e.m_act, sizeof(float) * GO2PI_SMALL_MAXB * m.out_dim);
-
-  const bool ln = has_ln(m);
-  // a layer past the first with more than 512 input columns: at batch 5 and up its input
-  // rows pass the 4096 granules one sweep round takes. The single launch and the
-  // resident act() form sweep a second round (their general instantiations,
-  // program.hpp program_small_general); the resident controller and recurrent forms do not
-  int kmax1 = 0;
-  for (int l = 1; l < p.nl; ++l) kmax1 = std::max(kmax1, p.L[l].K_pad);
-  const bool one_round = kmax1 <= 512;
-  // single-launch small-batch path: dense programs whose layers fit the kernel's
-  // register slots (K_pad <= 1024) and whose widest layer fits one resident grid
-  {
-    int kmax = 0;
-    for (int l = 0; l < p.nl; ++l) kmax = std::max(kmax, p.L[l].K_pad);
-    const bool lat_shape = kmax <= 1024 && go2pi::latency_grid(p) <= 256 && e.small_batch > 0 &&
-                           !sw.small_chain;  // (the switch: diagnostics, force the GEMV chain)
-    // (a LayerNormalization policy: only with opts.ln_small; latency_body normalises the
-    // swept rows as gemv_layer_kernel does)
-    e.latency_ok = !m.has_gru && lat_shape && (!ln || ln_small_on(e));
-    // the resident kernel's GRU / LSTM form (resident.hip, RNN): the cell tiled in front
-    // of the dense layers, h' carried between requests as granules (an LSTM's c in the
-    // owning workgroups' LDS)
-    const bool res_rnn = m.has_gru && ((m.gru.cell == 0 && m.gru.lbr == 1) || m.gru.cell == 1) && m.gru.H % 64 == 0 &&
-                         p.gru.I_pad + m.gru.H <= 512 && (m.gru.H >> 4) <= 256 && lat_shape && e.opts.resident_ms > 0 &&
-                         !ln && one_round;
-    e.palloc(&e.h_err, &e.m_err, 512);
-    p.err = e.m_err + 64;  // batched kernel hand-off timeouts
-    if (e.latency_ok || res_rnn) {
-      e.gstride = GO2PI_SMALL_MAXB * maxw;
-      const size_t ng = (size_t)std::max(1, p.nl - 1) * e.gstride;
-      e.d_gran = e.dalloc<unsigned long long>(ng);
-      hip_check(hipMemsetAsync(e.d_gran, 0, ng * sizeof(unsigned long long), e.stream), "hipMemsetAsync");
-      e.h_done = e.h_err + 32;  // 128 B apart: its own cache line
-      e.m_done = e.m_err + 32;
-      e.done_ok = p.L[p.nl - 1].N_pad == 16;
+  e.palloc(&e.h_err, &e.m_err, 512);
+  p.err = e.m_err + 64;  // batched kernel hand-off timeouts
+  if (plan.latency_ok || plan.res_rnn) {
+    e.gstride = GO2PI_SMALL_MAXB * maxw;
+    const size_t ng = (size_t)std::max(1, p.nl - 1) * e.gstride;
+    e.d_gran = e.dalloc<unsigned long long>(ng);
+    hip_check(hipMemsetAsync(e.d_gran, 0, ng * sizeof(unsigned long long), e.stream), "hipMemsetAsync");
+    e.h_done = e.h_err + 32;  // 128 B apart: its own cache line
+    e.m_done = e.m_err + 32;
+  }
+  if (plan.res_rnn && plan.done_ok) e.d_hgran = e.dalloc<unsigned long long>(2 * (size_t)GO2PI_SMALL_MAXB * p.gru.H);
+  // resident path: the latency kernel's program shape, the request ring in host memory
+  if (plan.resident(e.opts)) {
+    // room for a controller tick's rows too (GO2PI_CTL_RAW + in_dim floats per robot)
+    const size_t nreq = 1 + GO2PI_SMALL_MAXB * (size_t)(m.in_dim + GO2PI_CTL_RAW);
+    size_t rb = sizeof(unsigned long long) * nreq;
+    if (void *bar = bar_take(e.device, rb, sw.req_host)) {  // large BAR: the ring in VRAM, written by the host
+      e.h_req = e.m_req = static_cast<unsigned long long *>(bar);
+      e.req_bar_bytes = rb;
+    } else {
+      e.palloc(&e.h_req, &e.m_req, sizeof(unsigned long long) * nreq);
     }
-    if (res_rnn && e.done_ok) e.d_hgran = e.dalloc<unsigned long long>(2 * (size_t)GO2PI_SMALL_MAXB * m.gru.H);
-    // resident path: the latency kernel's program shape, the request ring in host memory
-    if ((e.latency_ok || res_rnn) && e.done_ok && e.opts.resident_ms > 0) {
-      // room for a controller tick's rows too (GO2PI_CTL_RAW + in_dim floats per robot)
-      const size_t nreq = 1 + GO2PI_SMALL_MAXB * (size_t)(m.in_dim + GO2PI_CTL_RAW);
-      size_t rb = sizeof(unsigned long long) * nreq;
-      if (void *bar = bar_take(e.device, rb, sw.req_host)) {  // large BAR: the ring in VRAM, written by the host
-        e.h_req = e.m_req = static_cast<unsigned long long *>(bar);
-        e.req_bar_bytes = rb;
-      } else {
-        e.palloc(&e.h_req, &e.m_req, sizeof(unsigned long long) * nreq);
-      }
-      // (the controller form's answer granules too: ctl_gran)
-      e.n_actg = std::max((size_t)GO2PI_SMALL_MAXB * m.out_dim, (size_t)go2pi::ctl_gran(m.in_dim).total);
-      e.palloc(&e.h_actg, &e.m_actg, sizeof(unsigned long long) * e.n_actg);
-      e.d_mirror = e.dalloc<unsigned long long>(1 + GO2PI_SMALL_MAXB * (size_t)m.in_dim);
-      int khz = 0;
-      hip_check(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, e.device), "hipDeviceGetAttribute");
-      if (khz <= 0) khz = 100000;
-      e.res_idle_ticks = (unsigned long long)e.opts.resident_ms * (unsigned long long)khz;
-      e.resident_ok = true;
-      res_register(&e);
-    }
+    // (the controller form's answer granules too: ctl_gran)
+    e.n_actg = std::max((size_t)GO2PI_SMALL_MAXB * m.out_dim, (size_t)go2pi::ctl_gran(m.in_dim).total);
+    e.palloc(&e.h_actg, &e.m_actg, sizeof(unsigned long long) * e.n_actg);
+    e.d_mirror = e.dalloc<unsigned long long>(1 + GO2PI_SMALL_MAXB * (size_t)m.in_dim);
+    int khz = 0;
+    hip_check(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, e.device), "hipDeviceGetAttribute");
+    if (khz <= 0) khz = 100000;
+    e.res_idle_ticks = (unsigned long long)e.opts.resident_ms * (unsigned long long)khz;
+    e.resident_ok = true;
+    res_register(&e);
   }
   // GO2PI_EPOCH0=<u32>: the engine's first granule tag instead of 1 (diagnostics and tests: a
   // value near 2^32 puts the tag-space wrap of next_epoch / resident_serve a few calls away
@@ -1145,109 +834,30 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
     p.stamps = e.dalloc<unsigned long long>(e.n_stamps);
     hip_check(hipMemsetAsync(p.stamps, 0, e.n_stamps * sizeof(unsigned long long), e.stream), "hipMemsetAsync");
   }
-  // the finished program, copied to device memory for the latency kernel
   {
     float *z = e.dalloc<float>(64);
     hip_check(hipMemsetAsync(z, 0, 64 * sizeof(float), e.stream), "hipMemsetAsync");
     p.zero = z;
   }
-  // controller tick: a policy with kHistory x 49 observations and 12 actions
-  if (m.in_dim > 0 && m.in_dim % GO2PI_CTL_STEP_DIM == 0 && m.in_dim <= 16 * GO2PI_CTL_STEP_DIM &&
-      m.out_dim == GO2PI_CTL_DOF) {
-    e.ctl_hist = m.in_dim / GO2PI_CTL_STEP_DIM;
+  if (e.ctl_hist) {  // controller tick
     e.d_ctl = e.dalloc<go2pi::DevCtlParams>(1);
     go2pi_ctl_params cp;
     go2pi_ctl_default_params(&cp);
     set_ctl_params(e, cp);
   }
   p.yield = yield_word(e.device);
-  // the pipeline's hot block (program.hpp): what it reads, in one scalar burst
-  if (p.w4_tpw) {
-    const auto &H = p.L[p.nl - 1];
-    p.l0_w = p.L[0].w;
-    p.head_w = H.w;
-    p.head_bias = H.bias;
-    p.bpack = p.w4_bpack;
-    p.zero_hot = p.zero;
-    p.err_hot = p.err;
-    p.nbias = p.w4_bias;
-    p.head_n = H.N;
-    p.c0 = p.L[0].K_pad / 16;
-    p.in_dim_hot = p.in_dim;
-    p.hid_act = p.L[0].act;
-    p.hid_alpha = p.L[0].alpha;
-    p.hid_beta = p.L[0].beta;
-    p.head_act = H.act;
-    p.head_alpha = H.alpha;
-    p.head_beta = H.beta;
-    p.post_plain = (!p.post_tanh && std::isinf(p.clip_lo) && p.clip_lo < 0 && std::isinf(p.clip_hi) &&
-                    p.clip_hi > 0 && p.scale == 1.f) ? 1 : 0;
-    p.w4_c0m = p.c0 % 4;
-    // the lean kernel: no prologue / epilogue arithmetic, no recurrent cell, and an
-    // LDS row no wider than the hidden layers
-    p.w4_plain = !p.has_gru && !p.pre_sub && !p.pre_div && !p.pre_mul && !p.pre_clip && !p.post_tanh &&
-                 std::isinf(p.clip_lo) && p.clip_lo < 0 && std::isinf(p.clip_hi) && p.clip_hi > 0 &&
-                 p.scale == 1.f && p.lds_stride == 64 * p.w4_tpw + 4 && !sw.no_plain;
-    // the lean kernel's compile-time activation: Elu (the exported rsl_rl / Isaac policies'), else runtime
-    // (1 = Elu with alpha 1, the ONNX default; any other alpha takes the runtime form)
-    p.w4_actc = (p.hid_act == 1 && p.hid_alpha == 1.f && !sw.lean_rt_act) ? 1 : -1;  // (the switch: A/B only)
-    // ... and its hidden-layer count (3: the usual policy depth): the layer loop fully
-    // unrolled, so no ring-register copies (and no vmcnt(0)) at the layer boundaries.
-    // The general body (recurrent policies) takes both only together.
-    p.w4_nhc = (p.w4_actc == 1 && p.nl - 1 == 3 && !sw.lean_rt_nh) ? 3 : 0;  // (the switch: A/B only)
-    if (!p.w4_plain && p.w4_nhc == 0) p.w4_actc = -1;
-    // the lean recurrent tick (policy_gru_kernel, r05; policy_lstm_kernel, r06): a GRU cell
-    // (lbr = 1) or an LSTM cell in front of a dense chain the lean kernel would serve
-    // (GO2PI_GRU_GENERAL=1 keeps the general body for both cells, A/B)
-    p.w4_gru_lean = (p.has_gru && ((p.gru.cell == 0 && p.gru.lbr == 1) || p.gru.cell == 1) &&
-                     (p.gru.H == 128 || p.gru.H == 256) &&
-                     p.gru.H <= 64 * p.w4_tpw && !p.pre_sub && !p.pre_div && !p.pre_mul && !p.pre_clip &&
-                     p.post_plain && p.lds_stride == 64 * p.w4_tpw + 4 && p.w4_actc == 1 && p.w4_nhc == 3 &&
-                     p.c0 == p.gru.H / 16 && p.gru.I_pad == (p.in_dim + 63) / 64 * 64 && p.in_dim < 4096 &&
-                     !p.zero_fill && !sw.gru_general) ? 1 : 0;
-  }
-  // the controller tick's general body instead of the lean tick kernel (A/B diagnostics,
-  // tests/test_gpu_controller.py::test_controller_tick_bodies)
-  p.ctl_general = sw.ctl_general ? 1 : 0;
-  // The resident kernel of each kind of request (program.hpp ResForm), decided here and
-  // nowhere else. Every policy with a resident path has the multi-workgroup kernel; a
-  // dense one takes a better form where one applies (GO2PI_RES_MULTI=1: never, A/B and
-  // the multi-workgroup form's tests):
-  //  - one workgroup, where the weights fit one CU's registers (no inter-workgroup hop per
-  //    layer): policy_act1_kernel wherever its shape applies (GO2PI_RES_R1W=1: never), else
-  //    r04's policy_resident1_kernel where that fits;
-  //  - act() of a wide policy (every hidden layer 256 or 512 wide: BASELINE configs[1]'s
-  //    48 -> 512^3 -> 12): policy_wide_kernel, when every workgroup can poll the request
-  //    ring in device memory (large BAR); else workgroup 0 of the multi-workgroup kernel
-  //    alone polls the host and mirrors the request.
-  // A LayerNormalization policy (opts.ln_small): of these, policy_act1_kernel's act() form
-  // only, and no resident controller form (its tick at batch <= 8: policy_latency_ctl_kernel).
-  // The controller form serves dense policies whose layer inputs fit one sweep round.
-  if (e.resident_ok) {
-    const bool better = !m.has_gru && !sw.res_multi;
-    const bool act1 = better && !sw.res_r1w && go2pi::resident_act1_fits(p);
-    e.res_act = ResForm::Multi;
-    if (act1) e.res_act = ResForm::Act1;
-    else if (better && !ln && go2pi::resident_r1_fits(p, false)) e.res_act = ResForm::R1;
-    else if (better && !ln && e.req_bar_bytes > 0 && go2pi::wide_shape(p).nl > 0) e.res_act = ResForm::Wide;
-    if (!m.has_gru && !ln && one_round) {
-      e.res_ctl = ResForm::Multi;
-      if (act1) e.res_ctl = ResForm::Act1;
-      else if (better && go2pi::resident_r1_fits(p, true)) e.res_ctl = ResForm::R1;
-    }
-  }
+  go2pi::fill_hot_block(p);  // (every pointer it mirrors is set)
+
+  const go2pi::ResForms res = go2pi::plan_resident(plan, sw, e.resident_ok, e.req_bar_bytes > 0);
+  e.res_act = res.act;
+  e.res_ctl = res.ctl;
   hip_check(go2pi::configure_kernels(p, e.waves), "hipFuncSetAttribute");
+  // the finished program, copied to device memory (what every kernel reads)
   e.d_prog = e.dalloc<go2pi::DevProgram>(1);
   hip_check(hipMemcpy(e.d_prog, &p, sizeof(p), hipMemcpyHostToDevice), "hipMemcpy");
   // (not hipDeviceSynchronize: that would wait for other engines' resident kernels)
   hip_check(hipStreamSynchronize(e.stream), "hipStreamSynchronize");
   hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
-
-  e.cost.flops_per_row = flops;
-  e.cost.weight_bytes = wbytes;
-  e.cost.io_bytes_per_row = 4.0 * (m.in_dim + m.out_dim) + (m.has_gru ? 8.0 * p.gru.sw : 0.0);
-  e.cost.n_layers = p.nl;
-  e.cost.has_gru = p.has_gru ? (p.gru.cell == 1 ? 2 : 1) : 0;  // 1 GRU, 2 LSTM (go2pi.h)
 }
 
 // Every C-ABI entry point runs through here: exceptions become status codes, and
@@ -1822,15 +1432,10 @@ int go2pi_resident_kernel(const go2pi_engine *e, char *buf, size_t cap) {
 }
 
 int go2pi_small_kernel(const go2pi_engine *e, char *buf, size_t cap) {
-  // (go2pi_run's selection at batch <= GO2PI_SMALL_MAXB: use_latency, use_graph, use_chain)
-  if (e && buf && cap && !e->latency_ok && !e->use_chain(1)) return go2pi_batched_kernel(e, buf, cap);
   return guarded([&] {
     check_engine(e);
     if (!buf || cap == 0) throw ApiError("null buffer", GO2PI_E_INVALID);
-    if (e->latency_ok)
-      std::snprintf(buf, cap, "%s", go2pi::latency_kernel_name());
-    else
-      std::snprintf(buf, cap, "%s%s", go2pi::gemv_kernel_name(), e->opts.use_graph ? " graph" : "");
+    go2pi::small_kernel_name(e->prog, e->waves, e->small_batch, e->latency_ok, e->opts.use_graph, buf, cap);
     return GO2PI_OK;
   });
 }

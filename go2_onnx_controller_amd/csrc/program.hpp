@@ -1,5 +1,5 @@
 // Device-side description of a loaded policy ("program"), passed to the HIP
-// kernels by value. Shared by engine.cpp (builds it) and kernels.hip (runs it).
+// kernels by value. Shared by plan.cpp (plans it), engine.cpp and kernels.hip (runs it).
 //
 // Weight layout in HBM ("fragment order", built once at load time):
 // a dense layer W[N][K] (ONNX Gemm transB=1 layout) is zero-padded to
@@ -289,7 +289,7 @@ int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned
                     float *hidden, const unsigned *yield, bool tiled0, void *stream);
 
 // The resident kernel that serves one kind of request (act(), or the controller tick) of an
-// engine, decided once when the engine is created (engine.cpp build): resident_start
+// engine, decided once when the engine is created (plan.cpp plan_resident): resident_start
 // launches it, resident_serve reads its answer accordingly, go2pi_resident_kernel names it.
 //   Act1   policy_act1_kernel (r05): one workgroup, a polling wave; answers in granules,
 //          the controller form too (actg holds ctl_gran(in_dim).total granules, each output

@@ -15,7 +15,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 
 def kernel_source_digest() -> str:
     """sha256 (first 16 hex) over every source that decides what the device runs and
-    the build flags: csrc/*.hip, *.hpp, *.inc (the kernels), engine.cpp and
+    the build flags: csrc/*.hip, *.hpp, *.inc (the kernels), engine.cpp, plan.cpp and
     onnx_model.cpp (weight packing and padding, kernel choice and launch shapes: a
     packing change moves the traffic as surely as a kernel change) and the
     Makefile, in name order."""

@@ -1,0 +1,119 @@
+// The engine's plan for a model, without a device: parse, plan (csrc/plan.hpp) and print
+// one JSON object with the kernels the engine would report and the plan's scalars.
+//
+//   plan_probe MODEL [key=value ...] [GO2PI_SWITCH[=value] ...] [ring=vram|host]
+//
+// key: a go2pi_opts field (waves, small_batch, resident_ms, ln_small, action_tanh,
+// obs_clip, action_clip, action_scale, use_graph; obs_mean / obs_std: one value for every
+// feature). A GO2PI_* argument is put into the environment and read by Switches::read(),
+// as an engine reads it. ring: where the resident request ring ended up (default vram).
+// A refusal prints {"error": ..., "code": ...} and exits 1. tests/test_cpu_plan.py runs it.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+#include <string>
+#include <vector>
+
+#include "plan.hpp"
+
+namespace {
+
+// FNV-1a over the floats' bytes: position-sensitive, so a pack in another order differs
+uint64_t fnv(const std::vector<float> &v) {
+  uint64_t h = 0xcbf29ce484222325ull;
+  const unsigned char *b = reinterpret_cast<const unsigned char *>(v.data());
+  for (size_t i = 0; i < v.size() * sizeof(float); ++i) h = (h ^ b[i]) * 0x100000001b3ull;
+  return h;
+}
+
+int run(int argc, char **argv) {
+  go2pi_opts o;
+  go2pi_default_opts(&o);
+  std::vector<float> mean, stdv;
+  bool ring_vram = true;
+  std::ifstream f(argv[1], std::ios::binary);
+  if (!f) throw go2pi::ApiError(std::string("cannot open model file '") + argv[1] + "'", GO2PI_E_MODEL);
+  const std::vector<uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  go2pi::Model m;
+  try {
+    m = go2pi::parse_onnx(bytes.data(), bytes.size());
+  } catch (const std::exception &ex) {
+    throw go2pi::ApiError(ex.what(), GO2PI_E_MODEL);
+  }
+  go2pi::check_model(m);
+  for (int i = 2; i < argc; ++i) {
+    const std::string a = argv[i];
+    const size_t eq = a.find('=');
+    const std::string k = a.substr(0, eq), v = eq == std::string::npos ? "1" : a.substr(eq + 1);
+    if (k.rfind("GO2PI_", 0) == 0) setenv(k.c_str(), v.c_str(), 1);
+    else if (k == "ring") ring_vram = v != "host";
+    else if (k == "waves") o.waves = std::atoi(v.c_str());
+    else if (k == "small_batch") o.small_batch = std::atoi(v.c_str());
+    else if (k == "resident_ms") o.resident_ms = std::atoi(v.c_str());
+    else if (k == "ln_small") o.ln_small = std::atoi(v.c_str());
+    else if (k == "use_graph") o.use_graph = std::atoi(v.c_str());
+    else if (k == "action_tanh") o.action_tanh = std::atoi(v.c_str());
+    else if (k == "obs_clip") o.obs_clip = std::strtof(v.c_str(), nullptr);
+    else if (k == "action_clip") o.action_clip = std::strtof(v.c_str(), nullptr);
+    else if (k == "action_scale") o.action_scale = std::strtof(v.c_str(), nullptr);
+    else if (k == "obs_mean") mean.assign(m.in_dim, std::strtof(v.c_str(), nullptr)), o.obs_mean = mean.data();
+    else if (k == "obs_std") stdv.assign(m.in_dim, std::strtof(v.c_str(), nullptr)), o.obs_std = stdv.data();
+    else throw go2pi::ApiError("plan_probe: unknown argument '" + a + "'", GO2PI_E_INVALID);
+  }
+  const go2pi::Switches sw = go2pi::Switches::read();
+  go2pi::Plan pl = go2pi::plan_program(m, o, sw);
+  const bool resident_ok = pl.resident(o);
+  const bool vram = resident_ok && ring_vram && !sw.req_host;  // (REQ_HOST: bar_take hands out no device block)
+  const go2pi::ResForms res = go2pi::plan_resident(pl, sw, resident_ok, vram);
+  go2pi::DevProgram &p = pl.prog;
+  // (the wide kernel's name says whether the policy has an observation prologue, which the
+  // launcher reads from these pointers; never dereferenced here)
+  p.pre_sub = pl.buf.pre_sub.empty() ? nullptr : pl.buf.pre_sub.data();
+  p.pre_div = pl.buf.pre_div.empty() ? nullptr : pl.buf.pre_div.data();
+  p.pre_mul = pl.buf.pre_mul.empty() ? nullptr : pl.buf.pre_mul.data();
+  char batched[128], small[128], ract[128], rctl[128];
+  go2pi::batched_kernel_name(p, pl.waves, batched, sizeof batched);
+  go2pi::small_kernel_name(p, pl.waves, pl.small_batch, pl.latency_ok, o.use_graph != 0, small, sizeof small);
+  go2pi::resident_kernel_name(res.act, p, vram, ract, sizeof ract);
+  go2pi::resident_kernel_name(res.ctl, p, vram, rctl, sizeof rctl);
+  std::printf("{\"batched_kernel\": \"%s\", \"small_kernel\": \"%s\", \"resident_kernel\": \"%s\", "
+              "\"controller_kernel\": \"%s\",\n",
+              batched, small, ract, rctl);
+  std::printf(" \"waves\": %d, \"w4_tpw\": %d, \"head_fuse\": %d, \"w4_c0m\": %d, \"w4_plain\": %d, \"w4_actc\": %d, "
+              "\"w4_nhc\": %d, \"w4_gru_lean\": %d, \"lds_stride\": %d, \"in_pad\": %d, \"zero_fill\": %d,\n",
+              pl.waves, p.w4_tpw, p.head_fuse, p.w4_c0m, p.w4_plain, p.w4_actc, p.w4_nhc, p.w4_gru_lean, p.lds_stride,
+              p.in_pad, p.zero_fill);
+  std::printf(" \"latency_ok\": %d, \"one_round\": %d, \"done_ok\": %d, \"ctl_hist\": %d, \"small_batch\": %d,\n",
+              (int)pl.latency_ok, (int)pl.one_round, (int)pl.done_ok, pl.ctl_hist, pl.small_batch);
+  std::printf(" \"cost\": {\"flops_per_row\": %.17g, \"weight_bytes\": %.17g, \"io_bytes_per_row\": %.17g, "
+              "\"n_layers\": %d, \"has_gru\": %d},\n",
+              pl.cost.flops_per_row, pl.cost.weight_bytes, pl.cost.io_bytes_per_row, (int)pl.cost.n_layers,
+              (int)pl.cost.has_gru);
+  std::printf(" \"bpack\": {\"len\": %zu, \"fnv\": \"%016llx\"}, \"bias\": [", pl.buf.bpack.size(),
+              (unsigned long long)fnv(pl.buf.bpack));
+  for (int l = 0; l < p.nl; ++l)
+    std::printf("%s{\"len\": %zu, \"fnv\": \"%016llx\"}", l ? ", " : "", pl.buf.bias[l].size(),
+                (unsigned long long)fnv(pl.buf.bias[l]));
+  std::printf("]}\n");
+  return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  if (argc < 2) {
+    std::fprintf(stderr, "usage: plan_probe MODEL [key=value ...] [GO2PI_SWITCH ...] [ring=vram|host]\n");
+    return 2;
+  }
+  try {
+    return run(argc, argv);
+  } catch (const go2pi::ApiError &ex) {
+    std::string msg;
+    for (const char *c = ex.what(); *c; ++c) msg += (*c == '"' || *c == '\\') ? std::string("\\") + *c : std::string(1, *c);
+    std::printf("{\"error\": \"%s\", \"code\": %d}\n", msg.c_str(), ex.code);
+    return 1;
+  }
+}

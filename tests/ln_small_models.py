@@ -32,7 +32,7 @@ NEW_MODELS = {
 ALL_MODELS = REGISTRY_MODELS + tuple(NEW_MODELS)
 
 # what serves go2pi_run at batch <= 8 with ln_small = 1 and resident_ms > 0, read from
-# engine.cpp's selection and resident.hip's act1_shape / launch_resident
+# plan.cpp's selection and resident.hip's act1_shape / launch_resident
 RESIDENT_FORM = {
     "ln_pre_small": "policy_act1_kernel",    # <3, 128, 1>: 100 and 72 of 128 columns
     "ln_ctl_post": "policy_act1_kernel",     # <4, 128, 2>, generic (not the Elu specialisation)

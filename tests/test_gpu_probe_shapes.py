@@ -5,9 +5,9 @@ summation order (tests/test_cpu_probe.py checks abs_sum_bound < 2^24, that the o
 agrees bit for bit and that no observation column or hidden unit goes unobserved), so
 each form must return `np.array_equal(y, int_ref)` for every request of its schedule: no
 tolerance that a dropped term, a stale row or an unswept row could hide in. The shapes
-sit on either side of the edges of the kernel-selection predicates (engine.cpp lat_shape
+sit on either side of the edges of the kernel-selection predicates (plan.cpp latency_shape
 / one_round / done_ok, kernels.hip latency_grid, resident.hip act1_shape /
-resident_r1_fits, resident_wide.hip wide_shape, engine.cpp w4_eligible / k0q / head
+resident_r1_fits, resident_wide.hip wide_shape, plan.cpp w4_eligible / k0q / head
 fusion); the tables below name the kernel each engine must report, and a resident engine
 must have served its whole schedule from one launch (a form that gives up on every
 request and is relaunched would otherwise pass).
