@@ -1932,17 +1932,29 @@ __device__ __forceinline__ void w4_gru_body(const DevProgram &P, const float *ob
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int row0 = blockIdx.x * GO2PI_TILE_ROWS;
-  // wave w stages rows w, w + 4, w + 8, w + 12; padding lanes read an element of the same
-  // row (times a zero weight column), rows past B the last row (their results are dropped)
+  // wave w stages rows w, w + 4, w + 8, w + 12; rows past B read the last row (their results
+  // are dropped). A padding lane (column k >= in_dim) reads a zero, as the general body's does:
+  // an element of the row would meet its zero weight column as 0 * Inf = NaN when it is
+  // infinite, where the cell saturates. The zero is the cell's own weight for the last padded
+  // column, ipad - 1 (unit 0, first gate), which pack_gru clears whenever in_dim < ipad, that
+  // is whenever there is a padding lane: fragments are [chunk k / 16][tile][gate]
+  // [lane 16 (k % 16 / 4)][k % 4]. One address from an argument already in registers, so
+  // nothing has to be fetched before the loads and every padding lane hits one cache line.
+  constexpr int CHF = (H / 16) * (LSTM ? 4 : 3) * 256;  // floats per 16-column chunk of the pack
+  const float *zero = gw + ((ipad >> 4) - 1) * CHF + 3 * 64 + 3;
+  // (the group loop outside the rows: the padding test once per group, not once per load)
   auto stage_obs = [&](int step) {
     const float *ob = obs + (size_t)step * B * in_dim;
+    const float *rp[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = wave + 4 * i;
-      const float *rp = ob + (size_t)min(row0 + r, B - 1) * in_dim;
-      for (int c = 0; c < nch; ++c)
-        __builtin_amdgcn_global_load_lds((gvoid_t *)(rp + min(c * 64 + lane, in_dim - 1)),
-                                         (lvoid_t *)(bufA + r * S + c * 64), 4, 0, 0);
+    for (int i = 0; i < 4; ++i) rp[i] = ob + (size_t)min(row0 + wave + 4 * i, B - 1) * in_dim + lane;
+#pragma unroll 1
+    for (int c = 0; c < nch; ++c) {
+      const bool pad = c * 64 + lane >= in_dim;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        __builtin_amdgcn_global_load_lds((gvoid_t *)(pad ? zero : rp[i] + c * 64),
+                                         (lvoid_t *)(bufA + (wave + 4 * i) * S + c * 64), 4, 0, 0);
     }
   };
   stage_obs(0);

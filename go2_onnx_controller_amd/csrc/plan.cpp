@@ -34,7 +34,9 @@ void pack_dense(const Dense &d, bool last, std::vector<float> &w, std::vector<fl
 
 // Recurrent-cell fragments: [Cx + Ch][Ht][gate][lane] float4 over the concatenated
 // [x (I_pad) | h (H)] axis; x chunks carry W, h chunks carry R. G = 3 gates (GRU:
-// z, r, h) or 4 (LSTM: i, o, f, c), in ONNX row order.
+// z, r, h) or 4 (LSTM: i, o, f, c), in ONNX row order. The x columns k >= I are zeros; the
+// lean recurrent tick's observation staging reads its padding lanes' zeros from them
+// (fused_impl.hpp w4_gru_body; tests/test_cpu_plan.py pins this layout).
 void pack_gru(const Gru &g, std::vector<float> &w, int &I_pad) {
   I_pad = ceil64(g.I);  // whole 4-chunk groups of x (the pipelined cell's ring runs on them)
   const int H = g.H, Ht = H / 16, Cx = I_pad / 16, Ch = H / 16, Cc = Cx + Ch, G = g.G;

@@ -97,7 +97,12 @@ int run(int argc, char **argv) {
   for (int l = 0; l < p.nl; ++l)
     std::printf("%s{\"len\": %zu, \"fnv\": \"%016llx\"}", l ? ", " : "", pl.buf.bias[l].size(),
                 (unsigned long long)fnv(pl.buf.bias[l]));
-  std::printf("]}\n");
+  std::printf("],\n");
+  // the recurrent cell's fragments and gate biases (empty without a cell)
+  std::printf(" \"gru_w\": {\"len\": %zu, \"fnv\": \"%016llx\"}, \"gru_bzr\": {\"len\": %zu, \"fnv\": \"%016llx\"}, "
+              "\"gru_bh\": {\"len\": %zu, \"fnv\": \"%016llx\"}}\n",
+              pl.buf.gru_w.size(), (unsigned long long)fnv(pl.buf.gru_w), pl.buf.gru_bzr.size(),
+              (unsigned long long)fnv(pl.buf.gru_bzr), pl.buf.gru_bh.size(), (unsigned long long)fnv(pl.buf.gru_bh));
   return 0;
 }
 

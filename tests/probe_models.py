@@ -18,6 +18,8 @@ not come from itself, tests/test_cpu_probe.py):
 Out of scope, because the observation cannot be injected exactly through them: the dense
 chain behind a GRU / LSTM cell, the controller-tick forms (an assembled observation) and
 LayerNormalization epilogues (a normalisation). Multi-GPU and timing are not probed.
+(The recurrent cell's own chunk walk is pinned against the fp64 oracle at every observation
+width and instantiation by tests/test_gpu_rnn_widths.py.)
 
 Points of the activation probes: +-0, then +- each of POINTS, the Clip bounds with their
 float32 neighbours, and HardSigmoid's two corners. Subnormal inputs and |x| >= 2^126 are

@@ -4,8 +4,9 @@ through tests/cpp/plan_probe.cpp: no device is touched.
 The expected kernel names are the GPU tests' own tables (imported, not copied): what a GPU
 run asserts of a live engine is asserted here of the plan, so a selection bug shows on a
 machine without a GPU. Then every diagnostic switch changes the reported kernel as
-plan.hpp's Switches says, the refusals keep their messages, and the pipeline's bias pack
-is the hidden layers' biases back to back.
+plan.hpp's Switches says, the refusals keep their messages, the pipeline's bias pack
+is the hidden layers' biases back to back, and the recurrent cell's fragment pack is
+pack_gru's layout, recomputed here in numpy.
 """
 import functools
 import json
@@ -22,6 +23,7 @@ import probe_models as pm
 import test_gpu_lean_tick as lean_tick
 import test_gpu_lean_transition as lean_transition
 import test_gpu_probe_activations as probe_act
+import test_gpu_rnn_widths as rnn_widths
 from conftest import ROOT, SHIPPED
 
 GEN8 = probe_act.GEN8
@@ -179,6 +181,19 @@ def test_gru_general(synth_path, tmp_path):
         assert got["batched_kernel"] == f"policy_fused_kernel<4, {tpw}, 1, 0, 0, 1, 3>" and got["w4_gru_lean"] == 0
 
 
+@pytest.mark.parametrize("case", rnn_widths.CASES, ids=rnn_widths._id)
+def test_rnn_width_cases(tmp_path, case):
+    """test_gpu_rnn_widths.py's table, of the plan: the kernel every case names (lean tick or
+    general body, its switches given as an engine would read them), and the LDS row and x
+    padding its staging relies on."""
+    p = _write(tmp_path, "rnn", rnn_widths.model_bytes(case))
+    got = plan(p, *[f"{k}={v}" for k, v in case.env], small_batch=-1)
+    assert got["batched_kernel"] == case.kernel
+    assert got["small_kernel"] == got["batched_kernel"]
+    assert (got["w4_gru_lean"], got["lds_stride"], got["in_pad"]) == rnn_widths.plan_scalars(case)
+    assert (got["waves"], got["w4_tpw"], got["zero_fill"]) == (4, case.head[0] // 64, 0)
+
+
 def test_small_chain():
     assert plan(SHIPPED)["small_kernel"] == "policy_latency_kernel"
     got = plan(SHIPPED, "GO2PI_SMALL_CHAIN", resident_ms=100)
@@ -248,3 +263,53 @@ def test_bias_pack_is_the_hidden_biases_back_to_back(synth_path):
     assert got["bias"] == [{"len": len(b), "fnv": _fnv(b)} for b in padded]
     assert got["bpack"] == {"len": 3 * 512, "fnv": _fnv(np.concatenate(biases[:3]))}
     assert plan(p, "GO2PI_NO_W4")["bpack"]["len"] == 0  # no pipeline, no pack
+
+
+# ---- 5. the recurrent cell's pack
+def _pack_gru(W, R, I, H, G):
+    """plan.cpp pack_gru in numpy: [Cx + Ch][Ht][gate][lane] float4 over the concatenated
+    [x (I padded to 64) | h] axis; lane l of tile t holds unit 16 t + (l & 15), columns
+    16 c + 4 (l >> 4) + j; x chunks from W (zeros for k >= I), h chunks from R."""
+    ipad = -(-I // 64) * 64
+    full = np.zeros((G * H, ipad + H), np.float32)
+    full[:, :I], full[:, ipad:] = W, R
+    a = full.reshape(G, H // 16, 16, (ipad + H) // 16, 4, 4)   # [gate, t, l & 15, c, l >> 4, j]
+    return a.transpose(3, 1, 0, 4, 2, 5).reshape(-1)            # [c, t, gate, l >> 4, l & 15, j]
+
+
+@pytest.mark.parametrize("H", [128, 256])
+@pytest.mark.parametrize("I", [1, 49, 98, 245])
+@pytest.mark.parametrize("cell", ["gru", "lstm"])
+def test_recurrent_pack_layout(tmp_path, cell, I, H):
+    """gru_w, gru_bzr and gru_bh as the cell reads them: lengths and FNVs of the numpy layout.
+    GRU: bzr the summed z and r biases, bh the candidate's input and recurrent biases apart;
+    LSTM: bzr the four summed gate biases (i, o, f, c), bh unused (zeros)."""
+    from go2_onnx_controller_amd import synth
+    seed, head = 40 + I + H, (256, 256, 256, 12)
+    if cell == "gru":
+        G, data = 3, synth.gru_model_bytes(I=I, H=H, head=head, seed=seed, lbr=1)
+        W, R, B = synth.gru_params(I, H, seed)
+        bzr = B[0, :2 * H] + B[0, 3 * H:5 * H]
+        bh = np.concatenate([B[0, 2 * H:3 * H], B[0, 5 * H:]])
+    else:
+        G, data = 4, synth.lstm_model_bytes(I=I, H=H, head=head, seed=seed)
+        W, R, B = synth.lstm_params(I, H, seed)
+        bzr, bh = B[0, :4 * H] + B[0, 4 * H:], np.zeros(2 * H, np.float32)
+    want = _pack_gru(W[0], R[0], I, H, G)
+    assert len(want) == (-(-I // 64) * 64 + H) * G * H
+    # the layout, spelled out for a few elements: (chunk, tile, gate, lane, j) -> W or R
+    ipad, Ht = -(-I // 64) * 64, H // 16
+    for c, t, g, lane, j in [(0, 0, 0, 0, 0), (0, Ht - 1, G - 1, 63, 3), (ipad // 16 - 1, 1, 1, 17, 2),
+                             (ipad // 16, 2, 0, 35, 1), ((ipad + H) // 16 - 1, Ht - 1, G - 1, 63, 3)]:
+        row, k = g * H + 16 * t + (lane & 15), 16 * c + 4 * (lane >> 4) + j
+        v = (W[0][row, k] if k < I else 0.0) if k < ipad else R[0][row, k - ipad]
+        assert want[((((c * Ht + t) * G + g) * 64 + lane) * 4) + j] == v
+    got = plan(_write(tmp_path, "cell", data))
+    assert got["gru_w"] == {"len": len(want), "fnv": _fnv(want)}
+    assert got["gru_bzr"] == {"len": len(bzr), "fnv": _fnv(bzr)}
+    assert got["gru_bh"] == {"len": len(bh), "fnv": _fnv(bh)}
+
+
+def test_no_cell_no_recurrent_pack():
+    got = plan(SHIPPED)
+    assert got["gru_w"]["len"] == got["gru_bzr"]["len"] == got["gru_bh"]["len"] == 0
