@@ -918,66 +918,53 @@ __device__ __forceinline__ void w4_wait(const int *flags, int wave, int ep, int 
   asm volatile("" ::: "memory");  // the LDS reads of the other waves' tiles stay after the wait
 }
 
-// GRU cell as the pipeline's front stage (one wave per SIMD): wave w owns hidden
-// tiles [w * GT, (w + 1) * GT) (H = 64 * GT) over the concatenated [x | h] chunks
-// (Cx = I_pad / 16 and Ch = H / 16, both multiples of 4: the engine pads I to 64).
-// The same register ring and buffer-load stream as the dense layers (RD = 1,
-// loads every 2 MFMAs), B operand one chunk ahead from LDS, output-major
-// accumulators (the gate fragment is the A operand): lane l holds units
-// 16t + 4(l >> 4) + e of robot l & 15, so the old h and the new h' move as one
-// float4 per tile. Gate math as gru_group (ONNX GRU, linear_before_reset = 1).
-// h' goes to Y rows and to hn (registers) for the caller. The caller has issued
-// the direct-to-LDS loads of x and h; this stage issues its first chunk's
-// fragments, waits for everything OLDER than them (the LDS-DMA), then barriers,
-// so the fragment latency overlaps the staging. Gate biases are added after the
-// contraction (accumulators start at zero), so their loads wait nowhere.
-// mid(): called between the contraction and the epilogue (the caller issues the next
-// stage's first loads there, so their latency overlaps the gate math).
-template <int GT, class Mid>
-__device__ __forceinline__ void w4_gru(const DevGru &G, const float *X, const float *Hs, float *Y, int xs, int wave,
-                                       int lane, float4 (&hn)[GT], unsigned long long *st, Mid &&mid) {
-  GO2PI_STAMP_AT(st, wave == 0 && lane == 0, 43);  // GRU stage marks (wave 0): 43 entry, 44 contraction, 45 epilogue
-  constexpr int NF = 3 * GT;  // gate fragments per chunk
-  constexpr int NM = 4 * NF;  // MFMAs per chunk
-  const int Cx = G.I_pad >> 4, Ch = G.H >> 4;
-  const int t0 = wave * GT, u0 = (lane >> 4) << 2;
+// The contraction of the pipelined recurrent cells (w4_gru, w4_lstm; one wave per
+// SIMD): wave w owns hidden tiles [w * GT, (w + 1) * GT) (H = 64 * GT) over the
+// concatenated [x | h] chunks (Cx = I_pad / 16 and Ch = H / 16, both multiples of 4:
+// the engine pads I to 64), NG gate fragments per (chunk, tile). The same register ring
+// and buffer-load stream as the dense layers (RD = 1, loads every 2 MFMAs), B operand
+// one chunk ahead from LDS, output-major accumulators (the gate fragment is the A
+// operand): lane l holds units 16t + 4(l >> 4) + e of robot l & 15. The caller has
+// issued the direct-to-LDS loads of x and h; this stage issues its first chunk's
+// fragments, waits for everything OLDER than them (the LDS-DMA), then barriers, so the
+// fragment latency overlaps the staging; post() runs once behind that barrier.
+// acc starts at zero: gate g of tile t0 + i sums into acc[g][i], but NG = 3's third
+// gate into acc[2] over the x chunks and acc[3] over the h chunks (the GRU's n_x, n_h).
+template <int NG, int GT, class Post>
+__device__ __forceinline__ void w4_cell_contract(const DevGru &G, const float *X, const float *Hs, int xs, int wave,
+                                                 int lane, f32x4 (&acc)[4][GT], Post &&post) {
+  static_assert(NG == 3 || NG == 4, "three gates (GRU) or four (LSTM)");
+  constexpr int NF = NG * GT, NM = 4 * NF;  // gate fragments and MFMAs per chunk
+  const int Cx = G.I_pad >> 4, Ch = G.H >> 4, t0 = wave * GT, u0 = (lane >> 4) << 2;
   const WStream ws(G.w);
-  const int csb = Ch * 3 * 1024;  // bytes per chunk (all tiles, three gates)
-  int vo[GT];                     // per-lane byte offset of tile t0 + i's z fragment in chunk 0 (r +1 KiB, n +2 KiB)
+  const int csb = Ch * NG * 1024;  // bytes per chunk (all tiles, NG gates)
+  int vo[GT];                      // per-lane byte offset of tile t0 + i's first gate fragment in chunk 0 (gate g +g KiB)
 #pragma unroll
-  for (int i = 0; i < GT; ++i) vo[i] = ((t0 + i) * 3 * 64 + lane) * 16;
+  for (int i = 0; i < GT; ++i) vo[i] = ((t0 + i) * NG * 64 + lane) * 16;
   // x chunks that hold data: Cxe = ceil(I / 16) (the packing pads x to whole 4-chunk
   // groups; a 48-wide observation leaves chunk 3 all zeros, skipped here: its 4 * NF
   // MFMAs are 1/20 of GRU-256's stage). With Cxe = 3 mod 4 the ring starts on slot 1
   // so that the h chunks start on slot 0 and keep their 4-chunk groups.
   const int Cxe = (G.I + 15) >> 4;
-  f32x4 z[GT], r[GT], nx[GT], nh[GT];
-  float4 bz[GT], br[GT], bx[GT], bh[GT];
-  const float *xrow = X + (lane & 15) * xs + u0;
-  const float *hrow = Hs + (lane & 15) * xs + u0;
+  const float *xrow = X + (lane & 15) * xs + u0, *hrow = Hs + (lane & 15) * xs + u0;
   auto run = [&](auto k0_k) {
     constexpr int K0S = decltype(k0_k)::value;  // ring slot of chunk 0
     float4 f[4][NF];
     asm volatile("" ::: "memory");  // the caller's LDS-DMA stays ahead of the NF loads
 #pragma unroll
-    for (int q = 0; q < NF; ++q) f[K0S][q] = ws.ld(vo[q / 3] + (q % 3) * 1024, 0);
+    for (int q = 0; q < NF; ++q) f[K0S][q] = ws.ld(vo[q / NG] + (q % NG) * 1024, 0);
     wg_barrier_vm<NF>();  // the x / h rows (LDS-DMA) have landed; chunk 0's fragments stay in flight
+    post();
 #pragma unroll
-    for (int i = 0; i < GT; ++i) {
-      const int j = (t0 + i) * 16 + u0;
-      bz[i] = *reinterpret_cast<const float4 *>(G.bzr + j);
-      br[i] = *reinterpret_cast<const float4 *>(G.bzr + G.H + j);
-      bx[i] = *reinterpret_cast<const float4 *>(G.bh + j);
-      bh[i] = *reinterpret_cast<const float4 *>(G.bh + G.H + j);
-      z[i] = r[i] = nx[i] = nh[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    for (int i = 0; i < GT; ++i)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g][i] = f32x4{0.f, 0.f, 0.f, 0.f};
     float4 a[2];
     a[K0S & 1] = *reinterpret_cast<const float4 *>(xrow);
-    // chunk c (slot S); XPH: an x chunk (the third gate accumulates n_x, else n_h);
-    // NEXT: a chunk follows, cn (its B operand and fragments are fetched here); NX:
-    // that chunk is an x chunk (else an h chunk). One fixed source row per
-    // instantiation keeps the B-operand read a single ds_read_b128.
-    auto chunk = [&](auto s_k, auto xph_k, auto next_k, auto nx_k, int c, int cn) {
+    // one chunk (slot S); XPH: an x chunk (else an h chunk: NG = 3's third gate); NEXT: a chunk
+    // follows, cn (its B operand and fragments are fetched here); NX: that chunk is an x chunk.
+    // One fixed source row per instantiation keeps the B-operand read a single ds_read_b128.
+    auto chunk = [&](auto s_k, auto xph_k, auto next_k, auto nx_k, int cn) {
       constexpr int S = decltype(s_k)::value;
       constexpr bool XPH = decltype(xph_k)::value, NEXT = decltype(next_k)::value, NX = decltype(nx_k)::value;
       if constexpr (NEXT) {
@@ -987,16 +974,13 @@ __device__ __forceinline__ void w4_gru(const DevGru &G, const float *X, const fl
       const float4 b = a[S & 1];
 #pragma unroll
       for (int m = 0; m < NM; ++m) {
-        const int jk = m / NF, i = (m % NF) / 3, g = m % 3;
-        const float wv = f4c(f[S][i * 3 + g], jk), bk = f4c(b, jk);
-        if (g == 0) z[i] = mfma4(wv, bk, z[i]);
-        else if (g == 1) r[i] = mfma4(wv, bk, r[i]);
-        else if (XPH) nx[i] = mfma4(wv, bk, nx[i]);
-        else nh[i] = mfma4(wv, bk, nh[i]);
+        const int jk = m / NF, i = (m % NF) / NG, g = m % NG;
+        const int ga = (NG == 3 && g == 2 && !XPH) ? 3 : g;
+        acc[ga][i] = mfma4(f4c(f[S][i * NG + g], jk), f4c(b, jk), acc[ga][i]);
         if (NEXT && (m & 1) == 1 && (m >> 1) < NF) {
           const int q = m >> 1;
           __builtin_amdgcn_sched_barrier(0);
-          f[(S + 1) & 3][q] = ws.ld(vo[q / 3] + (q % 3) * 1024, cn * csb);
+          f[(S + 1) & 3][q] = ws.ld(vo[q / NG] + (q % NG) * 1024, cn * csb);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -1010,44 +994,71 @@ __device__ __forceinline__ void w4_gru(const DevGru &G, const float *X, const fl
     int c = 0;
     if constexpr (K0S == 1) {  // a leading group of 3 x chunks (slots 1-3)
       if (Cxe > 3) {
-        chunk(I1{}, T_{}, T_{}, T_{}, 0, 1);
-        chunk(I2{}, T_{}, T_{}, T_{}, 1, 2);
-        chunk(I3{}, T_{}, T_{}, T_{}, 2, 3);
+        chunk(I1{}, T_{}, T_{}, T_{}, 1);
+        chunk(I2{}, T_{}, T_{}, T_{}, 2);
+        chunk(I3{}, T_{}, T_{}, T_{}, 3);
         c = 3;
       } else {
-        chunk(I1{}, T_{}, T_{}, T_{}, 0, 1);
-        chunk(I2{}, T_{}, T_{}, T_{}, 1, 2);
-        chunk(I3{}, T_{}, T_{}, F_{}, 2, Cx);  // the next chunk is the first h chunk
+        chunk(I1{}, T_{}, T_{}, T_{}, 1);
+        chunk(I2{}, T_{}, T_{}, T_{}, 2);
+        chunk(I3{}, T_{}, T_{}, F_{}, Cx);  // the next chunk is the first h chunk
         c = Cxe;
       }
     }
     if (c < Cxe) {
       for (; c + 4 < Cxe; c += 4) {
-        chunk(I0{}, T_{}, T_{}, T_{}, c, c + 1);
-        chunk(I1{}, T_{}, T_{}, T_{}, c + 1, c + 2);
-        chunk(I2{}, T_{}, T_{}, T_{}, c + 2, c + 3);
-        chunk(I3{}, T_{}, T_{}, T_{}, c + 3, c + 4);
+        chunk(I0{}, T_{}, T_{}, T_{}, c + 1);
+        chunk(I1{}, T_{}, T_{}, T_{}, c + 2);
+        chunk(I2{}, T_{}, T_{}, T_{}, c + 3);
+        chunk(I3{}, T_{}, T_{}, T_{}, c + 4);
       }
-      chunk(I0{}, T_{}, T_{}, T_{}, c, c + 1);
-      chunk(I1{}, T_{}, T_{}, T_{}, c + 1, c + 2);
-      chunk(I2{}, T_{}, T_{}, T_{}, c + 2, c + 3);
-      chunk(I3{}, T_{}, T_{}, F_{}, c + 3, Cx);  // the next chunk is the first h chunk
+      chunk(I0{}, T_{}, T_{}, T_{}, c + 1);
+      chunk(I1{}, T_{}, T_{}, T_{}, c + 2);
+      chunk(I2{}, T_{}, T_{}, T_{}, c + 3);
+      chunk(I3{}, T_{}, T_{}, F_{}, Cx);  // the next chunk is the first h chunk
     }
     for (c = Cx; c + 4 < Cx + Ch; c += 4) {
-      chunk(I0{}, F_{}, T_{}, F_{}, c, c + 1);
-      chunk(I1{}, F_{}, T_{}, F_{}, c + 1, c + 2);
-      chunk(I2{}, F_{}, T_{}, F_{}, c + 2, c + 3);
-      chunk(I3{}, F_{}, T_{}, F_{}, c + 3, c + 4);
+      chunk(I0{}, F_{}, T_{}, F_{}, c + 1);
+      chunk(I1{}, F_{}, T_{}, F_{}, c + 2);
+      chunk(I2{}, F_{}, T_{}, F_{}, c + 3);
+      chunk(I3{}, F_{}, T_{}, F_{}, c + 4);
     }
-    chunk(I0{}, F_{}, T_{}, F_{}, c, c + 1);
-    chunk(I1{}, F_{}, T_{}, F_{}, c + 1, c + 2);
-    chunk(I2{}, F_{}, T_{}, F_{}, c + 2, c + 3);
-    chunk(I3{}, F_{}, F_{}, F_{}, c + 3, c + 3);
+    chunk(I0{}, F_{}, T_{}, F_{}, c + 1);
+    chunk(I1{}, F_{}, T_{}, F_{}, c + 2);
+    chunk(I2{}, F_{}, T_{}, F_{}, c + 3);
+    chunk(I3{}, F_{}, F_{}, F_{}, c + 3);
   };
   if ((Cxe & 3) == 3) run(std::integral_constant<int, 1>{});
   else run(std::integral_constant<int, 0>{});
+}
+
+// GRU cell as the pipeline's front stage: w4_cell_contract over three gates (z, r, n),
+// then the gate math as gru_group (ONNX GRU, linear_before_reset = 1). h' goes to Y rows
+// and to hn (registers) for the caller. Gate biases are loaded behind the staging barrier
+// and added after the contraction, so their loads wait nowhere.
+// mid(): called between the contraction and the epilogue (the caller issues the next
+// stage's first loads there, so their latency overlaps the gate math).
+template <int GT, class Mid>
+__device__ __forceinline__ void w4_gru(const DevGru &G, const float *X, const float *Hs, float *Y, int xs, int wave,
+                                       int lane, float4 (&hn)[GT], unsigned long long *st, Mid &&mid) {
+  GO2PI_STAMP_AT(st, wave == 0 && lane == 0, 43);  // GRU stage marks (wave 0): 43 entry, 44 contraction, 45 epilogue
+  const int t0 = wave * GT, u0 = (lane >> 4) << 2;
+  f32x4 acc[4][GT];
+  const auto &z = acc[0], &r = acc[1], &nx = acc[2], &nh = acc[3];
+  float4 bz[GT], br[GT], bx[GT], bh[GT];
+  w4_cell_contract<3, GT>(G, X, Hs, xs, wave, lane, acc, [&] {
+#pragma unroll
+    for (int i = 0; i < GT; ++i) {
+      const int j = (t0 + i) * 16 + u0;
+      bz[i] = *reinterpret_cast<const float4 *>(G.bzr + j);
+      br[i] = *reinterpret_cast<const float4 *>(G.bzr + G.H + j);
+      bx[i] = *reinterpret_cast<const float4 *>(G.bh + j);
+      bh[i] = *reinterpret_cast<const float4 *>(G.bh + G.H + j);
+    }
+  });
   GO2PI_STAMP_AT(st, wave == 0 && lane == 0, 44);
   mid();
+  const float *hrow = Hs + (lane & 15) * xs + u0;
   float *yrow = Y + (lane & 15) * xs + t0 * 16 + u0;
 #pragma unroll
   for (int i = 0; i < GT; ++i) {
@@ -1067,111 +1078,17 @@ __device__ __forceinline__ void w4_gru(const DevGru &G, const float *X, const fl
   GO2PI_STAMP_AT(st, wave == 0 && lane == 0, 45);
 }
 
-// LSTM cell as the pipeline's front stage (one wave per SIMD), the sibling of
-// w4_gru: wave w owns hidden tiles [w * GT, (w + 1) * GT) (H = 64 * GT) over the
-// concatenated [x | h] chunks, four gate fragments per (chunk, tile) streamed by
-// the same register ring (RD = 1, a load every 2 MFMAs), output-major
-// accumulators: lane l holds units 16t + 4(l >> 4) + e of robot l & 15. The cell
-// state c of exactly those units lives in the caller's registers (c, in / out):
-// it is elementwise, so no other wave ever needs it and across the ticks of a
-// sequence it never leaves the CU. h' goes to Y rows and to hn.
+// LSTM cell as the pipeline's front stage, the sibling of w4_gru: w4_cell_contract
+// over four gates (i, o, f, c), then the gate math; the combined gate biases are
+// loaded here, in the epilogue. The cell state c of exactly the units a lane accumulates
+// lives in the caller's registers (c, in / out): it is elementwise, so no other wave needs
+// it and across the ticks of a sequence it never leaves the CU. h' goes to Y rows and hn.
 template <int GT, class Mid>
 __device__ __forceinline__ void w4_lstm(const DevGru &G, const float *X, const float *Hs, float *Y, int xs, int wave,
                                         int lane, float4 (&hn)[GT], float4 (&c)[GT], Mid &&mid) {
-  constexpr int NF = 4 * GT;  // gate fragments per chunk
-  constexpr int NM = 4 * NF;  // MFMAs per chunk
-  const int Cx = G.I_pad >> 4, Ch = G.H >> 4, H = G.H;
-  const int t0 = wave * GT, u0 = (lane >> 4) << 2;
-  const WStream ws(G.w);
-  const int csb = Ch * 4 * 1024;  // bytes per chunk (all tiles, four gates)
-  int vo[GT];
-#pragma unroll
-  for (int i = 0; i < GT; ++i) vo[i] = ((t0 + i) * 4 * 64 + lane) * 16;
-  // x chunks that hold data (as w4_gru: the all-zero padding chunk is skipped)
-  const int Cxe = (G.I + 15) >> 4;
+  const int H = G.H, t0 = wave * GT, u0 = (lane >> 4) << 2;
   f32x4 acc[4][GT];
-  const float *xrow = X + (lane & 15) * xs + u0;
-  const float *hrow = Hs + (lane & 15) * xs + u0;
-  auto run = [&](auto k0_k) {
-    constexpr int K0S = decltype(k0_k)::value;  // ring slot of chunk 0
-    float4 f[4][NF];
-    asm volatile("" ::: "memory");  // the caller's LDS-DMA stays ahead of the NF loads
-#pragma unroll
-    for (int q = 0; q < NF; ++q) f[K0S][q] = ws.ld(vo[q / 4] + (q % 4) * 1024, 0);
-    wg_barrier_vm<NF>();  // the x / h rows (LDS-DMA) have landed; chunk 0's fragments stay in flight
-#pragma unroll
-    for (int i = 0; i < GT; ++i)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float4 a[2];
-    a[K0S & 1] = *reinterpret_cast<const float4 *>(xrow);
-    // chunk cc (slot S); NEXT: a chunk follows, cn; NX: cn is an x chunk
-    auto chunk = [&](auto s_k, auto next_k, auto nx_k, int cc, int cn) {
-      constexpr int S = decltype(s_k)::value;
-      constexpr bool NEXT = decltype(next_k)::value, NX = decltype(nx_k)::value;
-      if constexpr (NEXT) {
-        if constexpr (NX) a[(S + 1) & 1] = *reinterpret_cast<const float4 *>(xrow + cn * 16);
-        else a[(S + 1) & 1] = *reinterpret_cast<const float4 *>(hrow + (cn - Cx) * 16);
-      }
-      const float4 b = a[S & 1];
-#pragma unroll
-      for (int m = 0; m < NM; ++m) {
-        const int jk = m / NF, i = (m % NF) / 4, g = m % 4;
-        acc[g][i] = mfma4(f4c(f[S][i * 4 + g], jk), f4c(b, jk), acc[g][i]);
-        if (NEXT && (m & 1) == 1 && (m >> 1) < NF) {
-          const int q = m >> 1;
-          __builtin_amdgcn_sched_barrier(0);
-          f[(S + 1) & 3][q] = ws.ld(vo[q / 4] + (q % 4) * 1024, cn * csb);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      (void)cc;
-    };
-    using T_ = std::true_type;
-    using F_ = std::false_type;
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    int cc = 0;
-    if constexpr (K0S == 1) {  // a leading group of 3 x chunks (slots 1-3)
-      if (Cxe > 3) {
-        chunk(I1{}, T_{}, T_{}, 0, 1);
-        chunk(I2{}, T_{}, T_{}, 1, 2);
-        chunk(I3{}, T_{}, T_{}, 2, 3);
-        cc = 3;
-      } else {
-        chunk(I1{}, T_{}, T_{}, 0, 1);
-        chunk(I2{}, T_{}, T_{}, 1, 2);
-        chunk(I3{}, T_{}, F_{}, 2, Cx);  // the next chunk is the first h chunk
-        cc = Cxe;
-      }
-    }
-    if (cc < Cxe) {
-      for (; cc + 4 < Cxe; cc += 4) {
-        chunk(I0{}, T_{}, T_{}, cc, cc + 1);
-        chunk(I1{}, T_{}, T_{}, cc + 1, cc + 2);
-        chunk(I2{}, T_{}, T_{}, cc + 2, cc + 3);
-        chunk(I3{}, T_{}, T_{}, cc + 3, cc + 4);
-      }
-      chunk(I0{}, T_{}, T_{}, cc, cc + 1);
-      chunk(I1{}, T_{}, T_{}, cc + 1, cc + 2);
-      chunk(I2{}, T_{}, T_{}, cc + 2, cc + 3);
-      chunk(I3{}, T_{}, F_{}, cc + 3, Cx);  // the next chunk is the first h chunk
-    }
-    for (cc = Cx; cc + 4 < Cx + Ch; cc += 4) {
-      chunk(I0{}, T_{}, F_{}, cc, cc + 1);
-      chunk(I1{}, T_{}, F_{}, cc + 1, cc + 2);
-      chunk(I2{}, T_{}, F_{}, cc + 2, cc + 3);
-      chunk(I3{}, T_{}, F_{}, cc + 3, cc + 4);
-    }
-    chunk(I0{}, T_{}, F_{}, cc, cc + 1);
-    chunk(I1{}, T_{}, F_{}, cc + 1, cc + 2);
-    chunk(I2{}, T_{}, F_{}, cc + 2, cc + 3);
-    chunk(I3{}, F_{}, F_{}, cc + 3, cc + 3);
-  };
-  if ((Cxe & 3) == 3) run(std::integral_constant<int, 1>{});
-  else run(std::integral_constant<int, 0>{});
+  w4_cell_contract<4, GT>(G, X, Hs, xs, wave, lane, acc, [] {});
   mid();
   float *yrow = Y + (lane & 15) * xs + t0 * 16 + u0;
 #pragma unroll
@@ -1195,6 +1112,29 @@ __device__ __forceinline__ void w4_lstm(const DevGru &G, const float *X, const f
     hn[i] = make_float4(o[0], o[1], o[2], o[3]);
     *reinterpret_cast<float4 *>(yrow + i * 16) = hn[i];
   }
+}
+
+// The state carry behind a pipelined cell, from its registers (hn, the LSTM's c): the
+// engine's state rows (SW floats, h | c) once, on the last tick, rows below B only; then,
+// behind the caller's barrier (every wave has read bufH), h' into the LDS hidden rows.
+template <int GT, bool LSTM>
+__device__ __forceinline__ void w4_state_store(float *hidden, int SW, int H, int row, int B, bool last, int wave,
+                                               int lane, const float4 (&hn)[GT], const float4 *c) {
+  if (!last || row >= B) return;
+  float *hg = hidden + (size_t)row * SW + wave * GT * 16 + ((lane >> 4) << 2);
+#pragma unroll
+  for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hg + i * 16) = hn[i];
+  if constexpr (LSTM) {
+#pragma unroll
+    for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hg + H + i * 16) = c[i];
+  }
+}
+
+template <int GT>
+__device__ __forceinline__ void w4_h_carry(float *bufH, int S, int wave, int lane, const float4 (&hn)[GT]) {
+  float *hl = bufH + (lane & 15) * S + wave * GT * 16 + ((lane >> 4) << 2);
+#pragma unroll
+  for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hl + i * 16) = hn[i];
 }
 
 // Launch-critical values of the pipeline, read in ONE scalar burst from the
@@ -1999,19 +1939,9 @@ __device__ __forceinline__ void w4_gru_body(const DevProgram &P, const float *ob
     auto mid = [&] { w4_prefill<TPW, 0>(l0w, ring0, wave, lane); };
     if constexpr (LSTM) w4_lstm<GT>(G, bufA, bufH, bufB, S, wave, lane, hn, creg, mid);
     else w4_gru<GT>(G, bufA, bufH, bufB, S, wave, lane, hn, nullptr, mid);
-    if (step == steps - 1 && row0 + (lane & 15) < B) {  // the engine's state: once, from registers
-      float *hg = hidden + (size_t)(row0 + (lane & 15)) * SW + wave * GT * 16 + ((lane >> 4) << 2);
-#pragma unroll
-      for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hg + i * 16) = hn[i];
-      if constexpr (LSTM) {
-#pragma unroll
-        for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hg + H + i * 16) = creg[i];
-      }
-    }
+    w4_state_store<GT, LSTM>(hidden, SW, H, row0 + (lane & 15), B, step == steps - 1, wave, lane, hn, creg);
     lds_barrier();  // every wave has read bufH (an LDS hand-off: no wait for the ring's loads)
-    float *hl = bufH + (lane & 15) * S + wave * GT * 16 + ((lane >> 4) << 2);
-#pragma unroll
-    for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hl + i * 16) = hn[i];
+    w4_h_carry<GT>(bufH, S, wave, lane, hn);
     // (the early hand-off in the GRU tick, where it was measured: GRU-256 55.9 -> 55.6 us per
     // tick, 5278 -> 5269 us per 100-tick launch; the LSTM tick keeps the parent's code)
     w4_step<TPW, HT, false, true, 0, 1, 3, 4, false, (!LSTM && TPW >= 4)>(P, hot, bufB, bufA, S, scratch, flags, lbias, ep, wave, lane,
@@ -2243,19 +2173,9 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
                        step == 0 ? srow : nullptr, mid);
           }
           ring_pre = PREF;
-          if (step == steps - 1 && row0 + (lane & 15) < B) {  // the engine's state: once, from registers
-            float *hg = hidden + (size_t)(row0 + (lane & 15)) * SW + wave * GT * 16 + ((lane >> 4) << 2);
-#pragma unroll
-            for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hg + i * 16) = hn[i];
-            if constexpr (lstm) {
-#pragma unroll
-              for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hg + H + i * 16) = creg[i];
-            }
-          }
+          w4_state_store<GT, lstm>(hidden, SW, H, row0 + (lane & 15), B, step == steps - 1, wave, lane, hn, creg);
           __syncthreads();  // every wave has read bufH
-          float *hl = bufH + (lane & 15) * S + wave * GT * 16 + ((lane >> 4) << 2);
-#pragma unroll
-          for (int i = 0; i < GT; ++i) *reinterpret_cast<float4 *>(hl + i * 16) = hn[i];
+          w4_h_carry<GT>(bufH, S, wave, lane, hn);
         };
         if (H == 256) {
           carry(std::integral_constant<int, 4>{});

@@ -2,7 +2,7 @@
 and in every instantiation that serves it, against the fp64 oracle.
 
 The cell walks the concatenated [x | h] axis in 16-column chunks through a 4-slot register
-ring. Which x chunks it walks, and on which slot it starts, depends on Cxe = ceil(I / 16):
+ring (w4_cell_contract, the one chunk schedule both cells call). Which x chunks it walks, and on which slot it starts, depends on Cxe = ceil(I / 16):
 
 * the ring starts on slot 1 when Cxe % 4 == 3 (so that the h chunks start on slot 0), else 0;
 * on slot 1 the leading group of three chunks is followed by more x chunks (Cxe > 3) or by h;
