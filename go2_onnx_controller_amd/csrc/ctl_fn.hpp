@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_fn.hpp"
+#include "lds_layout.hpp"
 #include "program.hpp"
 
 namespace go2pi {
@@ -100,26 +101,19 @@ struct CtlLds {
   unsigned *nanf;
 };
 
-// obs: the previous observation rows get a region of their own (false: the caller
-// places them, e.g. the batched kernel in its layer-0 output buffer, unused until the
-// assembly is done — at a 16-step history the rows are 50 KB per tile)
-__host__ __device__ inline int ctl_lds_floats(int R, int in_dim, bool obs = true) {
-  auto c64 = [](int x) { return (x + 63) & ~63; };
-  // q0: 12 doubles, copied by one direct-to-LDS instruction (64 lanes x 4 B: 64 floats of room)
-  return 64 + c64(R * GO2PI_CTL_STATE_DIM) + c64(R * GO2PI_CTL_JOY_DIM) + c64(R * GO2PI_CTL_DOF) +
-         (obs ? c64(R * in_dim) : 0) + GO2PI_TILE_ROWS;
-}
-
+// The image at `base` (16-byte aligned), its regions those of lds_layout.hpp ctl_image in
+// order (its size: ctl_lds_floats). obs: where the caller keeps the previous observation
+// rows; null: in the image's own region, in front of the flags.
 __device__ __forceinline__ CtlLds ctl_lds(float *base, int R, int in_dim, float *obs = nullptr) {
-  auto c64 = [](int x) { return (x + 63) & ~63; };
+  const CtlImage I = ctl_image(R, in_dim);
   CtlLds L;
   L.q0 = reinterpret_cast<double *>(base);
-  L.st = base + 64;
-  L.jy = L.st + c64(R * GO2PI_CTL_STATE_DIM);
-  L.act = L.jy + c64(R * GO2PI_CTL_JOY_DIM);
-  float *end = L.act + c64(R * GO2PI_CTL_DOF);
+  L.st = base + I.q0.size;
+  L.jy = L.st + I.st.size;
+  L.act = L.jy + I.jy.size;
+  float *end = L.act + I.act.size;
   L.obs = obs ? obs : end;
-  L.nanf = reinterpret_cast<unsigned *>(obs ? end : end + c64(R * in_dim));
+  L.nanf = reinterpret_cast<unsigned *>(obs ? end : end + I.obs.size);
   return L;
 }
 

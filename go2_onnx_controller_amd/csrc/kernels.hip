@@ -33,19 +33,19 @@ namespace go2pi {
 // Small-batch GEMV layer. grid = N_pad/16 workgroups (one per 16-output tile),
 // 8 waves split the K chunks. x: [B][x_stride] (device or host-mapped memory),
 // y: [B][y_stride]. Layer 0 applies the prologue; the final layer the epilogue.
-constexpr int GEMV_WAVES = 8;
+constexpr int GEMV_WAVES = lds::WAVES;
 
 __global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram P, int layer, const float *x,
                                                                      int x_stride, float *y, int y_stride, int B) {
   extern __shared__ float4 lds4[];
-  float *xs = reinterpret_cast<float *>(lds4);  // [B][K_pad]
   const DevLayer &L = P.L[layer];
   const int K_pad = L.K_pad, C = K_pad >> 4, T = L.N_pad >> 4;
   const int K = layer == 0 ? P.in_dim : P.L[layer - 1].N;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int t = blockIdx.x;
-  float *part = xs + GO2PI_SMALL_MAXB * K_pad;  // [GEMV_WAVES][B][16]
+  const GemvLds LY = gemv_lds(K_pad);
+  float *xs = reinterpret_cast<float *>(lds4), *part = xs + LY.xs.size;  // (the regions in LY's order)
   // Weights and bias do not depend on the input: issue their loads first so
   // their latency overlaps the input staging (wave w owns chunks w, w+8, ...).
   constexpr int MAXS = 8;  // chunk slots per wave: K_pad <= 8 * 8 * 16 = 1024 in registers
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram 
 // counter, correct for any workgroup->XCD placement). Tags = epoch0 + layer,
 // epoch0 advanced by the host every call, so granules of earlier calls never
 // match. Spins are bounded: on timeout the workgroup writes `err` and stops.
-constexpr int LAT_WAVES = 8;
+constexpr int LAT_WAVES = lds::WAVES;
 constexpr int LAT_MAXS = 8;  // chunk slots per wave held in registers (K_pad <= 1024)
 // the wave that sums a layer's partials and publishes it: the last one, since wave 0
 // alone sweeps a batch-1 layer input (its loads would complete behind its own stores)
@@ -183,15 +183,14 @@ __device__ __forceinline__ void latency_body(const DevProgram &P, const float *o
                                              unsigned epoch0, unsigned long long *gran, int gstride, unsigned *err,
                                              unsigned *done, const DevCtl ctl) {
   extern __shared__ float4 lds4[];
-  float *xs = reinterpret_cast<float *>(lds4);               // [B][K_pad] layer input
-  float *part = xs + GO2PI_SMALL_MAXB * P.lds_stride;        // [waves][B][16] partial sums
-  int &abort_flag = *reinterpret_cast<int *>(part + LAT_WAVES * GO2PI_SMALL_MAXB * 16);  // in the one LDS region
-  // CTL only: the new raw observation rows [B][in_dim], then the LDS image of the inputs
-  float *okeep = part + LAT_WAVES * GO2PI_SMALL_MAXB * 16 + 4;
+  const LatencyLds LY = latency_lds(P.lds_stride, 0);  // (the regions in LY's order; its total is the launcher's)
+  float *xs = reinterpret_cast<float *>(lds4), *part = xs + LY.xs.size;
+  int &abort_flag = *reinterpret_cast<int *>(part + LY.part.size);
+  float *okeep = part + LY.part.size + LY.flag.size;  // CTL: the regions of LatencyCtlLds
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (tid == 0) abort_flag = 0;
-  const CtlLds CL = ctl_lds(okeep + GO2PI_SMALL_MAXB * P.in_dim, GO2PI_SMALL_MAXB, P.in_dim);
+  const CtlLds CL = ctl_lds(okeep + latency_ctl_lds(P.in_dim).okeep.size, GO2PI_SMALL_MAXB, P.in_dim);
   CtlView cv{};
   CtlQ cq{};
   if constexpr (CTL) {
@@ -364,14 +363,17 @@ int latency_grid(const DevProgram &p) {
   return grid;
 }
 
+LatencyLds latency_lds_of(const DevProgram &p, bool ctl) {
+  return latency_lds(p.lds_stride, ctl ? latency_ctl_lds(p.in_dim).total : 0);
+}
+
 int launch_latency(const DevProgram &p, const DevProgram *p_dev, const float *obs, float *act, int batch,
                    unsigned epoch0,
                    unsigned long long *gran, int gstride, unsigned *err, unsigned *done, void *stream) {
   if (batch <= 0) return 0;
   if (batch > GO2PI_SMALL_MAXB) return (int)hipErrorInvalidValue;
   const int grid = latency_grid(p);
-  const size_t lds =
-      sizeof(float) * ((size_t)GO2PI_SMALL_MAXB * p.lds_stride + LAT_WAVES * GO2PI_SMALL_MAXB * 16 + 4);
+  const size_t lds = sizeof(float) * latency_lds_of(p, false).total;
   hipLaunchKernelGGL(program_small_general(p) ? policy_latency_ln_kernel : policy_latency_kernel, dim3(grid),
                      dim3(LAT_WAVES * 64), lds, reinterpret_cast<hipStream_t>(stream), p_dev, obs, act, batch, epoch0,
                      gran, gstride, err, done);
@@ -383,9 +385,7 @@ int launch_latency_ctl(const DevProgram &p, const DevProgram *p_dev, const DevCt
   if (batch <= 0) return 0;
   if (batch > GO2PI_SMALL_MAXB || p.L[p.nl - 1].N_pad != 16) return (int)hipErrorInvalidValue;
   const int grid = latency_grid(p);
-  const size_t lds = sizeof(float) * ((size_t)GO2PI_SMALL_MAXB * p.lds_stride + LAT_WAVES * GO2PI_SMALL_MAXB * 16 + 4 +
-                                      (size_t)GO2PI_SMALL_MAXB * p.in_dim + GO2PI_SMALL_MAXB +
-                                      ctl_lds_floats(GO2PI_SMALL_MAXB, p.in_dim));
+  const size_t lds = sizeof(float) * latency_lds_of(p, true).total;
   hipLaunchKernelGGL(program_small_general(p) ? policy_latency_ctl_ln_kernel : policy_latency_ctl_kernel, dim3(grid),
                      dim3(LAT_WAVES * 64), lds, reinterpret_cast<hipStream_t>(stream), p_dev, ctl, batch, epoch0, gran,
                      gstride, err, done);
@@ -401,9 +401,7 @@ size_t fused_lds_bytes(const DevProgram &p, int waves) {
          sizeof(float) * p.w4_bias;
 }
 
-size_t gemv_lds_bytes(const DevProgram &p, int layer) {
-  return sizeof(float) * ((size_t)GO2PI_SMALL_MAXB * p.L[layer].K_pad + GEMV_WAVES * GO2PI_SMALL_MAXB * 16);
-}
+GemvLds gemv_lds_of(const DevProgram &p, int layer) { return gemv_lds(p.L[layer].K_pad); }
 
 // The generic body's instantiations live in kernels_gen_w{4,8,16}.hip and the 4-wave
 // pipeline's in kernels_w4_t{2,4,8}.hip (one translation unit each, compiled in
@@ -434,7 +432,7 @@ int configure_kernels(const DevProgram &p, int waves) {
     e = (hipError_t)with_waves(waves, [&](auto w) { return gen_configure<decltype(w)::value>(p); });
   if (e != hipSuccess) return (int)e;
   int gmax = 0;
-  for (int l = 0; l < p.nl; ++l) gmax = std::max(gmax, (int)gemv_lds_bytes(p, l));
+  for (int l = 0; l < p.nl; ++l) gmax = std::max(gmax, (int)sizeof(float) * gemv_lds_of(p, l).total);
   e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemv_layer_kernel),
                           hipFuncAttributeMaxDynamicSharedMemorySize, gmax);
   return (int)e;
@@ -477,7 +475,7 @@ int launch_gemv_layer(const DevProgram &p, int layer, const float *x, int x_stri
   if (batch <= 0) return 0;
   if (batch > GO2PI_SMALL_MAXB) return (int)hipErrorInvalidValue;
   const dim3 grid(p.L[layer].N_pad >> 4);
-  hipLaunchKernelGGL(gemv_layer_kernel, grid, dim3(GEMV_WAVES * 64), gemv_lds_bytes(p, layer),
+  hipLaunchKernelGGL(gemv_layer_kernel, grid, dim3(GEMV_WAVES * 64), sizeof(float) * gemv_lds_of(p, layer).total,
                      reinterpret_cast<hipStream_t>(stream), p, layer, x, x_stride, y, y_stride, batch);
   return (int)hipGetLastError();
 }

@@ -19,6 +19,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "lds_layout.hpp"
+
 #define GO2PI_MAX_LAYERS 8
 #define GO2PI_TILE_ROWS 16      // robots per workgroup tile in the batched kernel
 #define GO2PI_SMALL_MAXB 8      // max rows of the GEMV chain
@@ -197,6 +199,10 @@ inline bool program_small_general(const DevProgram &p) {
 #define GO2PI_CTL_DOF 12
 #define GO2PI_CTL_STEP_DIM 49  // kDimObs, controller.hpp:14
 
+static_assert(lds::MAXB == GO2PI_SMALL_MAXB && lds::TILE == GO2PI_TILE_ROWS && lds::CTL_STATE == GO2PI_CTL_STATE_DIM &&
+                  lds::CTL_JOY == GO2PI_CTL_JOY_DIM && lds::CTL_DOF == GO2PI_CTL_DOF,
+              "lds_layout.hpp restates these constants");
+
 struct DevCtlParams {  // device memory, set by go2pi_ctl_set_params
   double q0[GO2PI_CTL_DOF];
   double action_scale;
@@ -224,7 +230,7 @@ int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves,
 size_t fused_lds_bytes(const DevProgram &p, int waves);
 int launch_gemv_layer(const DevProgram &p, int layer, const float *x, int x_stride, float *y, int y_stride,
                       int batch, void *stream);
-size_t gemv_lds_bytes(const DevProgram &p, int layer);
+GemvLds gemv_lds_of(const DevProgram &p, int layer);
 int configure_kernels(const DevProgram &p, int waves);
 // The instantiation launch_policy_fused runs for one tick of fewer than 2^20 rows, as
 // "kernel<template arguments>", printed by the dispatch that launches it.
@@ -242,6 +248,14 @@ int launch_latency(const DevProgram &p, const DevProgram *p_dev, const float *ob
                    unsigned epoch0,
                    unsigned long long *gran, int gstride, unsigned *err, unsigned *done, void *stream);
 int latency_grid(const DevProgram &p);
+// The dynamic-LDS layout (lds_layout.hpp) each small-batch launcher allocates and its
+// kernel addresses, of program p; ctl: the controller form. One function per form, next
+// to its launcher, which sizes the launch from it (tests/cpp/plan_probe.cpp prints them).
+LatencyLds latency_lds_of(const DevProgram &p, bool ctl);
+Act1Lds act1_lds_of(const DevProgram &p, bool ctl);  // Act1's shape applies (resident_act1_fits)
+R1Lds r1_lds_of(const DevProgram &p, bool ctl);
+MultiLds multi_lds_of(const DevProgram &p, bool ctl, bool tiled0);  // tiled0: as launch_resident's
+WideLds wide_lds_of(const DevProgram &p);            // wide_shape(p).nl != 0
 // Controller tick variants of the two launchers above (steps = 1; ctl.obs / ctl.action
 // replace obs / act). The latency variant needs the final layer to be one tile.
 int launch_policy_fused_ctl(const DevProgram &p, const DevProgram *p_dev, int waves, const DevCtl &ctl,

@@ -44,7 +44,7 @@ namespace go2pi {
 
 namespace {
 
-constexpr int RES_WAVES = 8;
+constexpr int RES_WAVES = lds::WAVES;
 constexpr int RES_MAXS = 8;  // chunk slots per wave held in registers (K_pad <= 1024)
 constexpr int RES_POLL = 2;  // header + observation granules per lane in the idle poll (<= 127 obs floats)
 constexpr int RES_GS = 4;    // GRU form: gate-fragment chunk slots per wave (I_pad + H <= 512)
@@ -204,7 +204,7 @@ __device__ __forceinline__ void local_layer0(const DevProgram &P, const float4 (
                                              float *x0, float *p0, float *xs, int B, int tid) {
   const DevLayer &L = P.L[0];
   // x0 rows hold NF / 4 chunks per slice (zero-padded past layer 0's own chunks)
-  const int N0 = L.N_pad, KS = (RES_WAVES * 64) / N0, K0 = (NF / 4) * KS * 16;
+  const int N0 = L.N_pad, KS = (RES_WAVES * 64) / N0, K0 = local0_row(NF, KS);
   for (int i = tid; i < B * K0; i += RES_WAVES * 64) {
     const int b = i / K0, k = i - b * K0;
     x0[i] = k < P.in_dim ? prologue(P, obsv[b * P.in_dim + k], k) : 0.f;
@@ -288,20 +288,14 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
   constexpr int NG = LSTM ? 4 : 3;  // gate fragments per (chunk, tile)
   const DevProgram &P = *Pd;
   extern __shared__ float4 lds4[];
-  float *xs = reinterpret_cast<float *>(lds4);                       // [B][K_pad] layer input
-  float *part = xs + GO2PI_SMALL_MAXB * P.lds_stride;                // [waves][B][16] partial sums
-  int *st = reinterpret_cast<int *>(part + RES_WAVES * GO2PI_SMALL_MAXB * 16);  // [0] leave, [1] epoch, [2] batch
-  float *obsv = reinterpret_cast<float *>(st + 4);                   // [B][in_dim] the request's observation
-  float *x0 = obsv + GO2PI_SMALL_MAXB * P.in_dim;                    // LOCAL0: [B][K0] prologued layer-0 input
-  // LOCAL0: x0 rows of NF / 4 chunks per k-slice (>= K_pad), then the KS > 1 partials [KS][B][N0]
-  const int x0len = LOCAL0 ? (NF / 4) * ((RES_WAVES * 64) / P.L[0].N_pad) * 16 : P.L[0].K_pad;
-  float *p0 = x0 + GO2PI_SMALL_MAXB * x0len;
-  // CTL: the LDS image of the tick's inputs (16-byte aligned: q0 is double)
-  // (p0's size: KS * MAXB * N0 floats when 512 / N0 = KS > 1 slices, as launch_resident reserves)
-  const int ks0 = ((RES_WAVES * 64) % P.L[0].N_pad == 0 && P.L[0].N_pad < RES_WAVES * 64) ? (RES_WAVES * 64) / P.L[0].N_pad : 0;
-  float *cbase = p0 + (ks0 * GO2PI_SMALL_MAXB * P.L[0].N_pad + 3) / 4 * 4;
+  // the regions: lds_layout.hpp MultiLds (no cell size: only the launcher needs the total)
+  const MultiLds LY = multi_lds(P.lds_stride, P.in_dim, P.L[0].K_pad, P.L[0].N_pad, NF, CTL, 0);
+  float *xs = reinterpret_cast<float *>(lds4), *part = xs + LY.xs.size;  // (each region behind the one before it)
+  int *st = reinterpret_cast<int *>(part + LY.part.size);
+  float *obsv = reinterpret_cast<float *>(st + LY.st.size), *x0 = obsv + LY.obsv.size, *p0 = x0 + LY.x0.size;
+  float *cbase = p0 + LY.p0.size;  // the controller's image, or the cell's regions
   const CtlLds CL = ctl_lds(cbase, GO2PI_SMALL_MAXB, P.in_dim);
-  float *craw = cbase + ctl_lds_floats(GO2PI_SMALL_MAXB, P.in_dim);  // CTL: [B][GO2PI_CTL_RAW + in_dim] request rows
+  float *craw = cbase + LY.image.size;
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int in_dim = P.in_dim;
@@ -311,21 +305,14 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
   // the batched-launch counter at launch (workgroup 0 leaves when it moves)
   const unsigned y0 =
       (g == 0 && yield) ? __hip_atomic_load(const_cast<unsigned *>(yield), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  // RNN: the cell's LDS (after the CTL regions: RNN and CTL are exclusive)
   const int Hh = RNN ? P.gru.H : 0, Ip = RNN ? P.gru.I_pad : 0, Kg = Ip + Hh, Cg = Kg >> 4, Cx = Ip >> 4;
   const int SW = RNN ? P.gru.sw : 0;  // state floats per robot row (LSTM: h | c)
   const int Ht = Hh >> 4;
-  float *hx = cbase;                                      // [B][Kg] the cell's input rows [x | h]
-  float *hpart = hx + GO2PI_SMALL_MAXB * Kg;              // [waves][4][B][16] partial sums (z, r, n_x, n_h)
-  unsigned *le = reinterpret_cast<unsigned *>(hpart + RES_WAVES * 4 * GO2PI_SMALL_MAXB * 16);  // [B] row epochs
-  unsigned *lb = le + GO2PI_SMALL_MAXB;                   // [B] the granule buffer holding each row's h
-  float *hown = reinterpret_cast<float *>(lb + GO2PI_SMALL_MAXB);  // [B][16] this workgroup's units' latest h'
-  float *cown = hown + GO2PI_SMALL_MAXB * 16;             // LSTM: [B][16] its units' cell state
-  // the cell's outputs of the request in flight, copied to hown / cown only once this
-  // workgroup has finished the request: a request abandoned mid-layers (a sweep met a
-  // LEAVE tag) then leaves the committed state, which the leave path writes back, as it was
-  float *hst = cown + GO2PI_SMALL_MAXB * 16;              // [B][16]
-  float *cst = hst + GO2PI_SMALL_MAXB * 16;               // LSTM: [B][16]
+  const CellLds CY = cell_lds(Ip, Hh);  // RNN: the cell's regions (lds_layout.hpp CellLds), in cbase's place
+  float *hx = cbase, *hpart = hx + CY.hx.size;
+  unsigned *le = reinterpret_cast<unsigned *>(hpart + CY.hpart.size), *lb = le + CY.le.size;
+  float *hown = reinterpret_cast<float *>(lb + CY.lb.size), *cown = hown + CY.hown.size;
+  float *hst = cown + CY.cown.size, *cst = hst + CY.hst.size;
   const size_t hbuf = (size_t)GO2PI_SMALL_MAXB * Hh;      // granules per buffer
   float4 wgf[RES_GS][NG];                                 // this workgroup's gate fragments (chunks wave + 8s)
   float gb[4] = {0.f, 0.f, 0.f, 0.f};                     // its biases: GRU z, r (summed), Wb_h, Rb_h; LSTM i, o, f, c
@@ -915,15 +902,12 @@ __global__ __launch_bounds__(NT) void policy_resident1_kernel(const DevProgram *
   const DevProgram &P = *Pd;
   extern __shared__ float4 lds4[];
   const int S = P.lds_stride;
-  float *x0 = reinterpret_cast<float *>(lds4);           // [8][S] layer 0's input rows (zero past in_dim)
-  float *xa = x0 + GO2PI_SMALL_MAXB * S;                 // [8][S] hidden layers' rows (ping-pong)
-  float *xb = xa + GO2PI_SMALL_MAXB * S;                 // [8][S]
-  int *st = reinterpret_cast<int *>(xb + GO2PI_SMALL_MAXB * S);  // [0] leave, [1] epoch, [2] batch, [3] word
-  float *obsv = reinterpret_cast<float *>(st + 4);       // [8][in_dim] the request's observation
-  // CTL: the LDS image of the tick's inputs (16-byte aligned: q0 is double), then the request rows
-  float *cbase = obsv + (GO2PI_SMALL_MAXB * P.in_dim + 3) / 4 * 4;
+  const R1Lds LY = r1_lds(S, P.in_dim, CTL);  // the regions: lds_layout.hpp R1Lds
+  float *x0 = reinterpret_cast<float *>(lds4), *xa = x0 + LY.x0.size, *xb = xa + LY.xa.size;  // (each behind the last)
+  int *st = reinterpret_cast<int *>(xb + LY.xb.size);
+  float *obsv = reinterpret_cast<float *>(st + LY.st.size), *cbase = obsv + LY.obsv.size;
   const CtlLds CL = ctl_lds(cbase, GO2PI_SMALL_MAXB, P.in_dim);
-  float *craw = cbase + ctl_lds_floats(GO2PI_SMALL_MAXB, P.in_dim);  // [B][GO2PI_CTL_RAW + in_dim]
+  float *craw = cbase + LY.image.size;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = 0;  // (RES_STAMP's workgroup index)
@@ -1214,24 +1198,20 @@ __global__ __launch_bounds__(a1_nt(CW)) void policy_act1_kernel(const DevProgram
   // they spilled
   // LN, four layers of 128: the same (the LN pass's registers beside all the weights
   // spilled 7 to 33 registers to scratch)
-  constexpr bool W0L = CTL || (LN && H == 128 && NL == 4);
+  constexpr bool W0L = act1_weights_in_lds(CTL, LN, H, NL);
   const DevProgram &P = *Pd;
   extern __shared__ float4 lds4[];
   const int S = P.lds_stride;
-  float *x0 = reinterpret_cast<float *>(lds4);  // [8][S] layer 0's input rows (zero past in_dim)
-  float *xa = x0 + GO2PI_SMALL_MAXB * S;        // [8][S] wide layers' rows (ping-pong)
-  float *xb = xa + GO2PI_SMALL_MAXB * S;
-  int *st = reinterpret_cast<int *>(xb + GO2PI_SMALL_MAXB * S);  // [0] leave, [1] epoch, [2] batch, [3] word
-  // CTL: the LDS image of the tick's inputs (q0 once, the request's rows per request),
-  // then layer 0's weights, lane-major [f][j][compute lane] float4 (a wave's read: 1 KiB
-  // contiguous)
-  const CtlLds CL = ctl_lds(reinterpret_cast<float *>(st + 4), GO2PI_SMALL_MAXB, P.in_dim);
-  float4 *w0l = reinterpret_cast<float4 *>(reinterpret_cast<float *>(st + 4) +
-                                           (CTL ? ctl_lds_floats(GO2PI_SMALL_MAXB, P.in_dim) : 0));
-  // CTL: the head's weights too (lane-major [f][head lane], 256 lanes), then the request's
-  // new observation rows [B][in_dim]
-  float4 *wol = w0l + (W0L ? F0 * R * 64 * CW : 0);
-  float *obsn = reinterpret_cast<float *>(wol + (W0L ? HF * 256 : 0));
+  const Act1Lds LY = act1_lds(S, P.in_dim, H, NL, F0, CTL, LN);  // the regions: lds_layout.hpp Act1Lds
+  static_assert(!W0L || (act1_lds(0, 0, H, NL, F0, CTL, LN).w0l.size == 4 * F0 * R * 64 * CW &&
+                         act1_lds(0, 0, H, NL, F0, CTL, LN).wol.size == 4 * HF * 256),
+                "the weights' LDS regions hold what the lanes write");
+  float *x0 = reinterpret_cast<float *>(lds4), *xa = x0 + LY.x0.size, *xb = xa + LY.xa.size;  // (each behind the last)
+  int *st = reinterpret_cast<int *>(xb + LY.xb.size);
+  float *cbase = reinterpret_cast<float *>(st + LY.st.size);
+  const CtlLds CL = ctl_lds(cbase, GO2PI_SMALL_MAXB, P.in_dim);
+  float4 *w0l = reinterpret_cast<float4 *>(cbase + LY.image.size), *wol = w0l + LY.w0l.size / 4;
+  float *obsn = reinterpret_cast<float *>(wol + LY.wol.size / 4);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = tid - 64;                // compute lane (the polling wave: negative)
@@ -1666,10 +1646,25 @@ A1Shape act1_shape(const DevProgram &p) {
   return a;
 }
 
-size_t resident1_lds_bytes(const DevProgram &p, bool ctl) {
-  size_t f = 3 * (size_t)GO2PI_SMALL_MAXB * p.lds_stride + 4 + ((size_t)GO2PI_SMALL_MAXB * p.in_dim + 3) / 4 * 4;
-  if (ctl) f += (size_t)ctl_lds_floats(GO2PI_SMALL_MAXB, p.in_dim) + (size_t)GO2PI_SMALL_MAXB * (GO2PI_CTL_RAW + p.in_dim);
-  return sizeof(float) * f;
+// One launch of a resident kernel with `floats` of dynamic LDS (a layout's total): refused
+// above a CU's 160 KiB, the kernel's limit raised where it passes the default 64 KiB.
+template <class K, class... A>
+int launch_with_lds(K kern, int grid, int nt, int floats, void *stream, A... args) {
+  const size_t lds = sizeof(float) * (size_t)floats;
+  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  if (lds > 64 * 1024) {
+    const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (a != hipSuccess) return (int)a;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), lds, reinterpret_cast<hipStream_t>(stream), args...);
+  return (int)hipGetLastError();
+}
+
+R1Lds r1_lds_of(const DevProgram &p, bool ctl) { return r1_lds(p.lds_stride, p.in_dim, ctl); }
+Act1Lds act1_lds_of(const DevProgram &p, bool ctl) {
+  const A1Shape a = act1_shape(p);
+  return act1_lds(p.lds_stride, p.in_dim, a.h, a.nl, a.f0, ctl, program_has_ln(p));
 }
 
 int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigned long long *req,
@@ -1681,17 +1676,9 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
   // a LayerNormalization program: policy_act1_kernel's act() form only (LN = true)
   const bool ln = program_has_ln(p);
   if (ln && (ctl || form != ResForm::Act1)) return (int)hipErrorInvalidValue;
-  const size_t lds = resident1_lds_bytes(p, ctl != nullptr);  // (r04's forms)
-  auto go = [&](auto kern, int nt) {
-    if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-      const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (a != hipSuccess) return (int)a;
-    }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(nt), lds, reinterpret_cast<hipStream_t>(stream), p_dev, req, actg,
-                       err, done, idle_ticks, yield, ctl ? *ctl : DevCtl{});
-    return (int)hipGetLastError();
+  auto go = [&](auto kern, int nt) {  // (r04's forms)
+    return launch_with_lds(kern, 1, nt, r1_lds_of(p, ctl != nullptr).total, stream, p_dev, req, actg, err, done,
+                           idle_ticks, yield, ctl ? *ctl : DevCtl{});
   };
   // the shipped model's shape (98 -> 128^3 -> 12: 4, 4, 4, 1 float4s per lane) has its own
   // instantiation: the registers it leaves free keep the controller form out of scratch
@@ -1700,29 +1687,11 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
   // r05: the polling-wave form (policy_act1_kernel), which the engine picks wherever its
   // shape applies (GO2PI_RES_R1W=1 at its creation: the r04 1024-thread form, A/B diagnostics)
   if (form == ResForm::Act1) {
-    // (the controller form: the assembly's image, layer 0's weights, lane-major, and the
-    // new observation rows besides)
-    const size_t lds1 = sizeof(float) * (3 * (size_t)GO2PI_SMALL_MAXB * p.lds_stride + 4 +
-                                         (ctl ? (size_t)ctl_lds_floats(GO2PI_SMALL_MAXB, p.in_dim) +
-                                                    (size_t)a1.f0 * (a1.h / 32) * 512 * 4 + (size_t)(a1.h / 64) * 256 * 4 +
-                                                    (size_t)GO2PI_SMALL_MAXB * p.in_dim
-                                              : 0) +
-                                         // (an LN program of four 128-wide layers: layer 0's and the
-                                         // head's weights in LDS, as the controller form keeps them)
-                                         ((!ctl && ln && a1.h == 128 && a1.nl == 4)
-                                              ? (size_t)a1.f0 * (a1.h / 32) * 512 * 4 + (size_t)(a1.h / 64) * 256 * 4
-                                              : 0));
     auto go1 = [&](auto kern, int cw) {
-      if (lds1 > 64 * 1024) {
-        const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-        if (a != hipSuccess) return (int)a;
-      }
       // (yield never null: the kernel loads it unconditionally, see a1_poll)
-      hipLaunchKernelGGL(kern, dim3(1), dim3(a1_nt(cw)), lds1, reinterpret_cast<hipStream_t>(stream), p_dev, req, actg,
-                         err, done, idle_ticks, yield ? yield : reinterpret_cast<const unsigned *>(p.zero),
-                         ctl ? *ctl : DevCtl{});
-      return (int)hipGetLastError();
+      return launch_with_lds(kern, 1, a1_nt(cw), act1_lds_of(p, ctl != nullptr).total, stream, p_dev, req, actg, err,
+                             done, idle_ticks, yield ? yield : reinterpret_cast<const unsigned *>(p.zero),
+                             ctl ? *ctl : DevCtl{});
     };
     const bool pro = p.pre_sub || p.pre_div || p.pre_mul || p.pre_clip;
     if (ln) return a1_generic_ln(a1, go1);
@@ -1753,6 +1722,18 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
   return go(policy_resident1_kernel<1024, R1_LMAX, 4, false>, 1024);
 }
 
+// local layer 0 where each thread's share of it fits NF = 8, 12 or 16 registers' fragments:
+// that NF, else 0 (layer 0 tiled)
+static int multi_nf(const DevProgram &p, bool tiled0) {
+  const int nf = local0_geometry(p.L[0].K_pad, p.L[0].N_pad).nf;
+  return (!p.has_gru && p.nl >= 2 && (nf == 8 || nf == 12 || nf == 16) && !tiled0) ? nf : 0;
+}
+
+MultiLds multi_lds_of(const DevProgram &p, bool ctl, bool tiled0) {
+  return multi_lds(p.lds_stride, p.in_dim, p.L[0].K_pad, p.L[0].N_pad, multi_nf(p, tiled0), ctl,
+                   p.has_gru ? cell_lds(p.gru.I_pad, p.gru.H).total : 0);
+}
+
 int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned long long *req,
                     unsigned long long *actg,
                     unsigned long long *gran, int gstride, unsigned long long *mirror, unsigned *err,
@@ -1766,37 +1747,15 @@ int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned
   if (rnn && (ctl || p.gru.cell > 1 || (!lstm && p.gru.lbr != 1) || p.gru.H % 64 ||
               p.gru.I_pad + p.gru.H > RES_GS * RES_WAVES * 16 || !hgran || !hidden))
     return (int)hipErrorInvalidValue;
-  // local layer 0 where each thread's share of it fits NF = 8, 12 or 16 registers'
-  // fragments (a slice's chunks past layer 0's own are zero fragments on zero columns)
-  const int N0 = p.L[0].N_pad, C0 = p.L[0].K_pad >> 4;
-  const int KS = (N0 > 0 && (RES_WAVES * 64) % N0 == 0) ? (RES_WAVES * 64) / N0 : 0;
-  const int nf = KS > 0 ? 4 * ((C0 + KS - 1) / KS) : 0;
-  const bool local0 = !rnn && p.nl >= 2 && (nf == 8 || nf == 12 || nf == 16) && !tiled0;
-  const int x0len = local0 ? (nf / 4) * KS * 16 : p.L[0].K_pad;
+  const int nf = multi_nf(p, tiled0);
+  const bool local0 = nf > 0;
   // one workgroup per 16-output tile of the widest TILED layer (with a local layer 0,
   // workgroups beyond the later layers' tiles would only repeat layer 0 and poll)
   int grid = rnn ? (p.gru.H >> 4) : 1;
   for (int l = local0 ? 1 : 0; l < p.nl; ++l) grid = std::max(grid, p.L[l].N_pad >> 4);
-  // (the kernel's LDS carve-up: x0 and p0 are laid out whether used or not)
-  const size_t ctl_off = ((size_t)GO2PI_SMALL_MAXB * p.lds_stride + RES_WAVES * GO2PI_SMALL_MAXB * 16 + 4 +
-                          (size_t)GO2PI_SMALL_MAXB * p.in_dim + (size_t)GO2PI_SMALL_MAXB * x0len +
-                          (size_t)(KS > 1 ? KS : 0) * GO2PI_SMALL_MAXB * N0 + 3) / 4 * 4;
-  size_t tail = 0;
-  if (ctl) tail = (size_t)ctl_lds_floats(GO2PI_SMALL_MAXB, p.in_dim) + (size_t)GO2PI_SMALL_MAXB * (GO2PI_CTL_RAW + p.in_dim);
-  if (rnn)
-    tail = (size_t)GO2PI_SMALL_MAXB * (p.gru.I_pad + p.gru.H) + RES_WAVES * 4 * GO2PI_SMALL_MAXB * 16 +
-           2 * GO2PI_SMALL_MAXB + 4 * GO2PI_SMALL_MAXB * 16;  // hown, cown, hst, cst (laid out for a GRU too)
-  const size_t lds = sizeof(float) * (ctl_off + tail);
-  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   auto go = [&](auto kern) {
-    if (lds > 64 * 1024) {
-      const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (a != hipSuccess) return (int)a;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(RES_WAVES * 64), lds, reinterpret_cast<hipStream_t>(stream), p_dev, req,
-                       actg, gran, gstride, mirror, err, done, idle_ticks, ctl ? *ctl : DevCtl{}, hgran, hidden, yield);
-    return (int)hipGetLastError();
+    return launch_with_lds(kern, grid, RES_WAVES * 64, multi_lds_of(p, ctl != nullptr, tiled0).total, stream, p_dev, req,
+                           actg, gran, gstride, mirror, err, done, idle_ticks, ctl ? *ctl : DevCtl{}, hgran, hidden, yield);
   };
   // the general instantiations: an LN program, or layer inputs past one sweep round
   // (engine.cpp selects neither the controller nor the recurrent form for those)

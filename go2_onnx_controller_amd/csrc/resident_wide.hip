@@ -232,13 +232,19 @@ __global__ __launch_bounds__(64 * (1 + CW)) void policy_wide_kernel(const DevPro
   constexpr int S0 = 4 * F0;    // layer 0's input row stride (floats)
   constexpr int MB = GO2PI_SMALL_MAXB;
   const DevProgram &P = *Pd;
+  // the regions (lds_layout.hpp WideLds), ordered and disjoint, the status words past the
+  // head products; the launcher never raises the dynamic-LDS limit
+  constexpr WideLds LY = wide_lds(CW, F0);
+  static_assert(LY.x0.off == 0 && LY.x0.end() <= LY.h0.off && LY.h0.end() <= LY.hh.off && LY.hh.end() <= LY.ho.off &&
+                    LY.ho.end() <= LY.pp.off && LY.pp.end() <= LY.st.off && LY.st.end() <= LY.total,
+                "policy_wide_kernel LDS regions");
+  static_assert(LY.x0.size == MB * S0 && LY.h0.size == MB * H && LY.pp.size == MB * 256 && LY.st.size >= 4,
+                "policy_wide_kernel LDS region sizes");
+  static_assert(LY.total * sizeof(float) <= 64 * 1024, "policy_wide_kernel LDS within the default limit");
   extern __shared__ float4 lds4[];
-  float *x0 = reinterpret_cast<float *>(lds4);  // [8][S0] the observation rows (prologued, zero-padded)
-  float *h0 = x0 + MB * S0;                     // [8][H] layer 0's outputs
-  float *hh = h0 + MB * H;                      // [8][H] a sliced layer's outputs of every workgroup (swept)
-  float *ho = hh + MB * H;                      // [8][16] this workgroup's outputs of a sliced layer
-  float *pp = ho + MB * 16;                     // [8][16 columns][16 head outputs] its head products
-  int *st = reinterpret_cast<int *>(pp + MB * 256);  // [0] leave [1] epoch [2] batch [3] fail
+  float *lds = reinterpret_cast<float *>(lds4);
+  float *x0 = lds + LY.x0.off, *h0 = lds + LY.h0.off, *hh = lds + LY.hh.off, *ho = lds + LY.ho.off, *pp = lds + LY.pp.off;
+  int *st = reinterpret_cast<int *>(lds + LY.st.off);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wg = blockIdx.x;
@@ -518,8 +524,9 @@ int wide_kernel_name(const DevProgram &p, char *buf, size_t cap) {
   return std::snprintf(buf, cap, "policy_wide_kernel<%d, %d, %d, %d>", w.nl, w.cw, w.f0, w.pro);
 }
 
-size_t wide_lds_bytes(const WideShape &w) {
-  return sizeof(float) * ((size_t)GO2PI_SMALL_MAXB * (4 * w.f0 + 2 * 64 * w.cw + 16 + 256) + 4);
+WideLds wide_lds_of(const DevProgram &p) {
+  const WideShape w = wide_shape(p);
+  return wide_lds(w.cw, w.f0);
 }
 
 int launch_resident_wide(const DevProgram &p, const DevProgram *p_dev, const unsigned long long *req,
@@ -527,7 +534,7 @@ int launch_resident_wide(const DevProgram &p, const DevProgram *p_dev, const uns
                          unsigned long long idle_ticks, const unsigned *yield, void *stream) {
   const WideShape w = wide_shape(p);
   if (!w.nl || !yield || gstride < GO2PI_SMALL_MAXB * 64 * w.cw) return (int)hipErrorInvalidValue;
-  const size_t lds = wide_lds_bytes(w);
+  const size_t lds = sizeof(float) * wide_lds_of(p).total;
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(4 * w.cw), dim3(64 * (1 + w.cw)), lds, reinterpret_cast<hipStream_t>(stream), p_dev,
                        req, actg, gran, gstride, err, done, idle_ticks, yield);

@@ -8,6 +8,9 @@
 // feature). A GO2PI_* argument is put into the environment and read by Switches::read(),
 // as an engine reads it. ring: where the resident request ring ended up (default vram).
 // A refusal prints {"error": ..., "code": ...} and exits 1. tests/test_cpu_plan.py runs it.
+// "lds": the dynamic-LDS layout (csrc/lds_layout.hpp) of every small-batch launcher the
+// plan uses, as its launcher sizes it: regions [name, offset, size] in floats, total_bytes,
+// and the arguments it was made from (tests/test_cpu_lds_layout.py).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +30,97 @@ uint64_t fnv(const std::vector<float> &v) {
   const unsigned char *b = reinterpret_cast<const unsigned char *>(v.data());
   for (size_t i = 0; i < v.size() * sizeof(float); ++i) h = (h ^ b[i]) * 0x100000001b3ull;
   return h;
+}
+
+// one layout as {"regions": [[name, offset, size], ...], "total_bytes": n, <args>}
+struct Regions {
+  std::string out;
+  void add(const char *name, go2pi::lds::Span s, int base = 0) {
+    out += (out.empty() ? "[\"" : ", [\"") + std::string(name) + "\", " + std::to_string(base + s.off) + ", " +
+           std::to_string(s.size) + "]";
+  }
+  void image(int in_dim, go2pi::lds::Span at) {  // the controller image's regions in place of `at`
+    const go2pi::CtlImage I = go2pi::ctl_image(GO2PI_SMALL_MAXB, in_dim);
+    if (at.size == 0) return;
+    add("image.q0", I.q0, at.off), add("image.st", I.st, at.off), add("image.jy", I.jy, at.off);
+    add("image.act", I.act, at.off), add("image.obs", I.obs, at.off), add("image.nanf", I.nanf, at.off);
+  }
+  void print(const char *key, int total, const std::string &args = "") const {
+    std::printf("  \"%s\": {\"regions\": [%s], \"total_bytes\": %zu%s}", key, out.c_str(), sizeof(float) * (size_t)total,
+                args.c_str());
+  }
+};
+
+void print_latency(const char *key, const go2pi::DevProgram &p, bool ctl) {
+  const go2pi::LatencyLds L = go2pi::latency_lds_of(p, ctl);
+  Regions r;
+  r.add("xs", L.xs), r.add("part", L.part), r.add("flag", L.flag);
+  if (ctl) {
+    const go2pi::LatencyCtlLds C = go2pi::latency_ctl_lds(p.in_dim);
+    r.add("okeep", C.okeep, L.ctl.off), r.image(p.in_dim, {L.ctl.off + C.image.off, C.image.size});
+    r.add("slack", C.slack, L.ctl.off);
+  }
+  r.print(key, L.total);
+}
+
+void print_resident(const char *key, go2pi::ResForm form, const go2pi::DevProgram &p, bool ctl, bool tiled0) {
+  Regions r;
+  char args[160] = "";
+  int total = 0;
+  if (form == go2pi::ResForm::Act1) {
+    const go2pi::Act1Lds L = go2pi::act1_lds_of(p, ctl);
+    r.add("x0", L.x0), r.add("xa", L.xa), r.add("xb", L.xb), r.add("st", L.st), r.image(p.in_dim, L.image);
+    r.add("w0l", L.w0l), r.add("wol", L.wol), r.add("obsn", L.obsn);
+    std::snprintf(args, sizeof args, ", \"form\": \"act1\", \"h\": %d, \"nl\": %d, \"f0\": %d", L.h, L.nl, L.f0);
+    total = L.total;
+  } else if (form == go2pi::ResForm::R1) {
+    const go2pi::R1Lds L = go2pi::r1_lds_of(p, ctl);
+    r.add("x0", L.x0), r.add("xa", L.xa), r.add("xb", L.xb), r.add("st", L.st), r.add("obsv", L.obsv);
+    r.image(p.in_dim, L.image), r.add("craw", L.craw);
+    std::snprintf(args, sizeof args, ", \"form\": \"r1\"");
+    total = L.total;
+  } else if (form == go2pi::ResForm::Wide) {
+    const go2pi::WideLds L = go2pi::wide_lds_of(p);
+    const go2pi::WideShape w = go2pi::wide_shape(p);
+    r.add("x0", L.x0), r.add("h0", L.h0), r.add("hh", L.hh), r.add("ho", L.ho), r.add("pp", L.pp), r.add("st", L.st);
+    std::snprintf(args, sizeof args, ", \"form\": \"wide\", \"cw\": %d, \"f0\": %d", w.cw, w.f0);
+    total = L.total;
+  } else {
+    const go2pi::MultiLds L = go2pi::multi_lds_of(p, ctl, tiled0);
+    r.add("xs", L.xs), r.add("part", L.part), r.add("st", L.st), r.add("obsv", L.obsv), r.add("x0", L.x0);
+    r.add("p0", L.p0), r.image(p.in_dim, L.image), r.add("craw", L.craw);
+    if (p.has_gru) {
+      const go2pi::CellLds C = go2pi::cell_lds(p.gru.I_pad, p.gru.H);
+      r.add("hx", C.hx, L.cell.off), r.add("hpart", C.hpart, L.cell.off), r.add("le", C.le, L.cell.off);
+      r.add("lb", C.lb, L.cell.off), r.add("hown", C.hown, L.cell.off), r.add("cown", C.cown, L.cell.off);
+      r.add("hst", C.hst, L.cell.off), r.add("cst", C.cst, L.cell.off);
+    }
+    std::snprintf(args, sizeof args, ", \"form\": \"multi\", \"nf\": %d, \"tiled0\": %d", L.nf, (int)tiled0);
+    total = L.total;
+  }
+  r.print(key, total, args);
+}
+
+void print_lds(const go2pi::DevProgram &p, const go2pi::ResForms &res, bool latency_ok, bool tiled0) {
+  std::printf(" \"lds\": {\"lds_stride\": %d, \"in_dim\": %d, \"nl\": %d, \"k0_pad\": %d, \"n0_pad\": %d, \"ln\": %d, "
+              "\"rnn\": %d, \"i_pad\": %d, \"gru_h\": %d,\n  \"gemv\": [",
+              p.lds_stride, p.in_dim, p.nl, p.L[0].K_pad, p.L[0].N_pad, (int)go2pi::program_has_ln(p), p.has_gru,
+              p.has_gru ? p.gru.I_pad : 0, p.has_gru ? p.gru.H : 0);
+  for (int l = 0; l < p.nl; ++l) {
+    const go2pi::GemvLds L = go2pi::gemv_lds_of(p, l);
+    Regions r;
+    r.add("xs", L.xs), r.add("part", L.part);
+    std::printf("%s{\"k_pad\": %d, \"regions\": [%s], \"total_bytes\": %zu}", l ? ", " : "", p.L[l].K_pad, r.out.c_str(),
+                sizeof(float) * (size_t)L.total);
+  }
+  std::printf("]");
+  if (latency_ok) {
+    std::printf(",\n"), print_latency("latency", p, false);
+    std::printf(",\n"), print_latency("latency_ctl", p, true);
+  }
+  if (res.act != go2pi::ResForm::None) std::printf(",\n"), print_resident("act", res.act, p, false, tiled0);
+  if (res.ctl != go2pi::ResForm::None) std::printf(",\n"), print_resident("ctl", res.ctl, p, true, tiled0);
+  std::printf("},\n");
 }
 
 int run(int argc, char **argv) {
@@ -98,6 +192,7 @@ int run(int argc, char **argv) {
     std::printf("%s{\"len\": %zu, \"fnv\": \"%016llx\"}", l ? ", " : "", pl.buf.bias[l].size(),
                 (unsigned long long)fnv(pl.buf.bias[l]));
   std::printf("],\n");
+  print_lds(p, res, pl.latency_ok, sw.res_tiled0);
   // the recurrent cell's fragments and gate biases (empty without a cell)
   std::printf(" \"gru_w\": {\"len\": %zu, \"fnv\": \"%016llx\"}, \"gru_bzr\": {\"len\": %zu, \"fnv\": \"%016llx\"}, "
               "\"gru_bh\": {\"len\": %zu, \"fnv\": \"%016llx\"}}\n",
