@@ -781,6 +781,7 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
     hip_check(hipMemsetAsync(e.d_hidden, 0, nh * sizeof(float), e.stream), "hipMemsetAsync");
   }
   p.w4_bpack = opt_upload(buf.bpack);
+  const float *lnpack = opt_upload(buf.lnpack);  // the LN pipeline's pack (program.hpp w4ln_tpw)
   p.pre_sub = opt_upload(buf.pre_sub);
   p.pre_div = opt_upload(buf.pre_div);
   p.pre_mul = opt_upload(buf.pre_mul);
@@ -847,6 +848,7 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   }
   p.yield = yield_word(e.device);
   go2pi::fill_hot_block(p);  // (every pointer it mirrors is set)
+  if (p.w4ln_tpw) p.bpack = lnpack;
 
   const go2pi::ResForms res = go2pi::plan_resident(plan, sw, e.resident_ok, e.req_bar_bytes > 0);
   e.res_act = res.act;

@@ -26,6 +26,7 @@
 // identical instruction sequence wherever it sits in the batch: sharded and
 // unsharded runs are bit-identical.
 #include "fused_impl.hpp"
+#include "w4ln_layout.hpp"
 
 namespace go2pi {
 
@@ -424,8 +425,24 @@ static int with_w4(const DevProgram &p, F &&f) {
   }
 }
 
+// the 4-wave LayerNormalization pipeline (kernels_w4ln_t{2,4,8}.hip), DevProgram::w4ln_tpw
+template <class F>
+static int with_w4ln(const DevProgram &p, F &&f) {
+  switch (p.w4ln_tpw) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
 int configure_kernels(const DevProgram &p, int waves) {
   hipError_t e = hipSuccess;
+  // (an LN pipeline program: its batched kernel, and the general body too, which serves its
+  // controller tick)
+  if (p.w4ln_tpw) {
+    e = (hipError_t)with_w4ln(p, [&](auto t) { return w4ln_configure<decltype(t)::value>(p); });
+    if (e != hipSuccess) return (int)e;
+  }
   if (waves == 4 && p.w4_tpw)
     e = (hipError_t)with_w4(p, [&](auto t) { return w4_configure<decltype(t)::value>(p); });
   else
@@ -441,6 +458,10 @@ int configure_kernels(const DevProgram &p, int waves) {
 int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves, const float *obs, float *act,
                         float *hidden, int batch, int steps, void *stream) {
   if (batch <= 0 || steps <= 0) return 0;
+  if (p.w4ln_tpw)
+    return with_w4ln(p, [&](auto t) {
+      return w4ln_launch<decltype(t)::value>(p, p_dev, obs, act, batch, steps, stream);
+    });
   if (waves == 4 && p.w4_tpw)
     return with_w4(p, [&](auto t) {
       return w4_launch<decltype(t)::value>(p, p_dev, obs, act, hidden, batch, steps, stream);
@@ -451,6 +472,7 @@ int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves,
 }
 
 int batched_kernel_name(const DevProgram &p, int waves, char *buf, size_t cap) {
+  if (p.w4ln_tpw) return with_w4ln(p, [&](auto t) { return w4ln_name<decltype(t)::value>(p, buf, cap); });
   if (waves == 4 && p.w4_tpw) return with_w4(p, [&](auto t) { return w4_name<decltype(t)::value>(p, buf, cap); });
   return with_waves(waves, [&](auto w) { return gen_name<decltype(w)::value>(p, buf, cap); });
 }

@@ -1,6 +1,7 @@
 // The engine's planner (plan.hpp): model + options + switches -> the program's scalars, the
 // host buffers behind its pointers, and which kernel serves what. No HIP in here.
 #include "plan.hpp"
+#include "w4ln_layout.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -60,6 +61,20 @@ void pack_gru(const Gru &g, std::vector<float> &w, int &I_pad) {
           }
 }
 
+// The pipeline's shape test (w4_eligible below; the LN pipeline, plan_program): the tiles per
+// wave (2, 4 or 8) of a policy whose dense layers it serves, else 0.
+int w4_shape_tpw(const Model &m) {
+  const int nl = (int)m.layers.size();
+  if (nl < 2) return 0;
+  const int tpw = ceil64(m.layers[0].N) / 64, t_last = ceil16(m.layers[nl - 1].N) / 16;
+  if (!(tpw == 2 || tpw == 4 || tpw == 8) || t_last > (tpw == 8 ? 1 : 2)) return 0;
+  for (int l = 0; l + 1 < nl; ++l)
+    if (ceil64(m.layers[l].N) != 64 * tpw || m.layers[l].act != m.layers[0].act ||
+        m.layers[l].alpha != m.layers[0].alpha || m.layers[l].beta != m.layers[0].beta)
+      return 0;
+  return tpw;
+}
+
 // The 4-wave uniform-MLP pipeline (fused_impl.hpp w4_step) applies to a policy
 // whose hidden layers are all 64 * TPW wide (TPW = 2, 4 or 8) with one
 // activation, and whose final layer is at most 2 tiles wide (1 at TPW = 8); a GRU
@@ -75,15 +90,15 @@ bool w4_eligible(const Model &m, const go2pi_opts &o, const Switches &sw, bool l
   if (m.has_gru && m.gru.H % 64) return false;
   if (m.has_gru && m.gru.cell == 0 && m.gru.lbr == 0) return false;  // the two-pass cell: generic body only
   if (sw.no_head_fuse || sw.no_w4) return false;  // A/B diagnostics only
-  if (ln) return false;  // LayerNormalization: the general body only (fused_impl.hpp ln_tile)
-  const int tpw = ceil64(m.layers[0].N) / 64, t_last = ceil16(m.layers[nl - 1].N) / 16;
-  if (!(tpw == 2 || tpw == 4 || tpw == 8) || t_last > (tpw == 8 ? 1 : 2)) return false;
-  for (int l = 0; l + 1 < nl; ++l)
-    if (ceil64(m.layers[l].N) != 64 * tpw || m.layers[l].act != m.layers[0].act ||
-        m.layers[l].alpha != m.layers[0].alpha || m.layers[l].beta != m.layers[0].beta)
-      return false;
-  return true;
+  // LayerNormalization: the general body (fused_impl.hpp ln_tile), or, with opts.ln_small's
+  // GO2PI_LN_BATCHED bit, the pipeline's LN kernel beside it (plan_program, w4ln_tpw)
+  if (ln) return false;
+  return w4_shape_tpw(m) != 0;
 }
+
+// opts.ln_small as its two bits (GO2PI_LN_SMALL | GO2PI_LN_BATCHED); any value outside 0..3
+// reads as 0: the field fills the earlier layout's tail padding, which may hold anything
+int ln_bits(const go2pi_opts &o) { return o.ln_small >= 0 && o.ln_small <= 3 ? o.ln_small : 0; }
 
 // no action post-processing (tanh / clip / scale): the head's plain store
 bool post_plain(const DevProgram &p) {
@@ -106,7 +121,7 @@ void check_model(const Model &m) {
 }
 
 void fill_hot_block(DevProgram &p) {
-  if (!p.w4_tpw) return;
+  if (!p.w4_tpw && !p.w4ln_tpw) return;
   const auto &H = p.L[p.nl - 1];
   p.l0_w = p.L[0].w;
   p.head_w = H.w;
@@ -125,6 +140,15 @@ void fill_hot_block(DevProgram &p) {
   p.head_alpha = H.alpha;
   p.head_beta = H.beta;
   p.post_plain = post_plain(p) ? 1 : 0;
+  if (p.w4ln_tpw) {
+    // the LN pipeline (program.hpp w4ln_tpw): the model's hidden activation (the planner moved
+    // a pre-LN layer's to its ln_act), and the pack's floats; bpack is set by build()
+    const DevLayer &L0 = p.L[0];
+    p.hid_act = L0.ln == 1 ? L0.ln_act : L0.act;
+    p.hid_alpha = L0.ln == 1 ? L0.ln_alpha : L0.alpha;
+    p.hid_beta = L0.ln == 1 ? L0.ln_beta : L0.beta;
+    p.nbias = 3 * (p.nl - 1) * 64 * p.w4ln_tpw;
+  }
 }
 
 Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
@@ -308,10 +332,9 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   // register slots (K_pad <= 1024) and whose widest layer fits one resident grid
   pl.latency_shape = std::max(kmax1, p.L[0].K_pad) <= 1024 && latency_grid(p) <= 256 && pl.small_batch > 0 &&
                      !sw.small_chain;  // (the switch: diagnostics, force the GEMV chain)
-  // (a LayerNormalization policy: only with opts.ln_small, exactly 1: the field fills the
-  // earlier layout's tail padding; latency_body normalises the swept rows as
-  // gemv_layer_kernel does)
-  pl.latency_ok = !m.has_gru && pl.latency_shape && (!pl.has_ln || o.ln_small == 1);
+  // (a LayerNormalization policy: only with opts.ln_small's GO2PI_LN_SMALL bit, ln_bits;
+  // latency_body normalises the swept rows as gemv_layer_kernel does)
+  pl.latency_ok = !m.has_gru && pl.latency_shape && (!pl.has_ln || (ln_bits(o) & GO2PI_LN_SMALL));
   // the resident kernel's GRU / LSTM form (resident.hip, RNN): the cell tiled in front
   // of the dense layers, h' carried between requests as granules (an LSTM's c in the
   // owning workgroups' LDS)
@@ -324,6 +347,28 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
       m.out_dim == GO2PI_CTL_DOF)
     pl.ctl_hist = m.in_dim / GO2PI_CTL_STEP_DIM;
 
+  // The pipeline's LN kernel (w4ln_impl.hpp policy_mlp_ln_kernel) for batched launches, with
+  // opts.ln_small's GO2PI_LN_BATCHED bit: a dense LN policy of the pipeline's shape and the
+  // lean kernel's conditions (no prologue constants or clip, no action post-processing, an
+  // observation no wider than the hidden layers). The program stays the general body's in
+  // every other respect, so the controller tick, the GEMV chain, the single launch and the
+  // resident forms run what they run without the bit. Anything else keeps the general body.
+  if ((ln_bits(o) & GO2PI_LN_BATCHED) && pl.has_ln && !m.has_gru && o.waves == 0 && !sw.no_w4 && !sw.no_head_fuse) {
+    const int tpw = w4_shape_tpw(m), nh = p.nl - 1;
+    const bool bare = buf.pre_sub.empty() && buf.pre_div.empty() && buf.pre_mul.empty() && !p.pre_clip &&
+                      post_plain(p) && p.lds_stride == 64 * tpw + 4;
+    if (tpw && bare && p.in_dim < 4096 && p.L[0].K_pad / 16 < 256 && (p.L[0].K_pad / 16) % 4 == 0 &&
+        sizeof(float) * (size_t)w4ln_lds(tpw, p.L[nh].N_pad / 16, nh).total <= (size_t)W4LN_MAX_LDS_BYTES) {
+      p.w4ln_tpw = tpw;
+      const size_t W = 64 * (size_t)tpw;
+      buf.lnpack.assign(3 * nh * W, 0.f);
+      for (int l = 0; l < nh; ++l) {
+        std::copy(buf.bias[l].begin(), buf.bias[l].end(), buf.lnpack.begin() + l * W);
+        std::copy(buf.ln_g[l].begin(), buf.ln_g[l].end(), buf.lnpack.begin() + (nh + l) * W);
+        std::copy(buf.ln_b[l].begin(), buf.ln_b[l].end(), buf.lnpack.begin() + (2 * nh + l) * W);
+      }
+    }
+  }
   // the pipeline's hot block (program.hpp): what it reads, in one scalar burst
   fill_hot_block(p);
   if (p.w4_tpw) {

@@ -67,6 +67,7 @@ struct HostBuffers {
   std::vector<size_t> off;
   std::vector<float> bias[GO2PI_MAX_LAYERS], ln_g[GO2PI_MAX_LAYERS], ln_b[GO2PI_MAX_LAYERS];  // [N_pad] each
   std::vector<float> bpack;      // the pipeline's bias pack (w4_bpack): the hidden layers' biases back to back
+  std::vector<float> lnpack;     // the LN pipeline's pack (program.hpp w4ln_tpw): biases | Scale | B of the hidden layers
   std::vector<float> gru_w, gru_bzr, gru_bh;
   std::vector<float> pre_sub, pre_div, pre_mul;
 };
@@ -94,8 +95,9 @@ void check_model(const Model &m);
 // The plan of model m under options o (defaults applied) and switches sw. Throws ApiError
 // for a combination of options and graph that is not supported.
 Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw);
-// The hot block's mirror of the program's other fields (program.hpp), pipeline programs
-// only: filled here and nowhere else. plan_program calls it for the scalars, build() again
+// The hot block's mirror of the program's other fields (program.hpp), pipeline and LN
+// pipeline (w4ln_tpw) programs only: filled here and nowhere else (the LN pack's pointer,
+// bpack, by build()). plan_program calls it for the scalars, build() again
 // once the pointers are set.
 void fill_hot_block(DevProgram &p);
 

@@ -116,7 +116,8 @@ struct DevProgram {
   // ---- hot block (the first 80 bytes): every field the 4-wave pipeline reads,
   // so that one scalar burst at kernel start fetches all of it (the fields'
   // scattered lazy loads were a chain of ~7 dependent scalar round trips before
-  // the first observation load; fused_impl.hpp W4Hot). Set for pipeline programs.
+  // the first observation load; fused_impl.hpp W4Hot). Set for pipeline programs, and
+  // for the LN pipeline's (w4ln_tpw below).
   const float *l0_w;       // = L[0].w, the base of the packed dense layers (back to back)
   const float *head_w;     // = L[nl - 1].w
   const float *head_bias;  // = L[nl - 1].bias
@@ -139,6 +140,15 @@ struct DevProgram {
   int zero_fill;   // 1: clear LDS activation buffers at kernel start (padded columns never written)
   int w4_tpw;      // >0: 4-wave uniform-MLP pipeline (kernels.hip, w4_step), tiles per wave of every hidden layer
   int w4_bias;     // pipeline: LDS floats holding every hidden layer's bias (sum of their N_pad), else 0
+  // >0: batched launches run the 4-wave LayerNormalization pipeline (w4ln_impl.hpp
+  // policy_mlp_ln_kernel; opts.ln_small bit GO2PI_LN_BATCHED) with this many tiles per wave
+  // (2 / 4 / 8). The program stays the general body's in every other field (waves 8, w4_tpw
+  // 0, layer 0 padded to 64), so every other launch of the engine runs what it runs without
+  // the bit; the hot block is filled as for the pipeline, with hid_act the MODEL's hidden
+  // activation (a pre-LN layer's DevLayer::act is none), bpack the LN pack and nbias its
+  // floats: [3][nl - 1][64 tpw], the hidden biases back to back, then every hidden layer's
+  // Scale, then every hidden layer's B (zeros for a layer without LN).
+  int w4ln_tpw;
   const float *w4_bpack;  // pipeline: those biases packed back to back in device memory (one LDS-DMA stream)
   int w4_plain;           // pipeline, 1: no prologue / epilogue arithmetic, no recurrent cell (the lean kernel)
   int w4_gru_lean;        // 1: a GRU policy served by the lean GRU tick (policy_gru_kernel, r05)
@@ -166,6 +176,14 @@ struct DevProgram {
                                // move leaves (it holds CUs the batched kernel needs; resident.hip)
   DevLayer L[GO2PI_MAX_LAYERS];
 };
+
+// gemv_layer_kernel takes the program by value: a field appended to it moves that kernel's
+// other arguments (and its code). w4ln_tpw fills what was padding in front of w4_bpack, and
+// the LayerNormalization pipeline reads everything else it needs from the hot block and from
+// the layers' own LN fields.
+static_assert(offsetof(DevProgram, w4ln_tpw) == 124 && offsetof(DevProgram, w4_bpack) == 128 &&
+                  offsetof(DevProgram, L) == 312 && sizeof(DevProgram) == 312 + GO2PI_MAX_LAYERS * sizeof(DevLayer),
+              "the program's layout is every kernel's ABI");
 
 // a LayerNormalization on any layer (host side: which instantiation a launcher picks)
 inline bool program_has_ln(const DevProgram &p) {

@@ -164,7 +164,7 @@ class Engine:
 
     def __init__(self, model, device=0, max_batch=4096, use_graph=True, waves=0, small_batch=0,
                  obs_mean=None, obs_std=None, obs_clip=0.0, action_tanh=False, action_clip=0.0,
-                 action_scale=0.0, log_level=2, resident_ms=0, ln_small=False):
+                 action_scale=0.0, log_level=2, resident_ms=0, ln_small=False, ln_batched=False):
         L = lib()
         o = Opts()
         L.go2pi_default_opts(ctypes.byref(o))
@@ -184,7 +184,9 @@ class Engine:
         o.resident_ms = int(resident_ms)  # > 0: batch <= 8 run() served by a resident kernel
         # a LayerNormalization policy at batch <= 8: the single-launch kernel and, with
         # resident_ms > 0, a resident kernel (False: one launch per layer)
-        o.ln_small = int(bool(ln_small))
+        # ln_batched: batched launches of a dense LN policy of the pipeline's shape on
+        # policy_mlp_ln_kernel (False: the general batched kernel). go2pi.h GO2PI_LN_SMALL | GO2PI_LN_BATCHED
+        o.ln_small = int(bool(ln_small)) | 2 * int(bool(ln_batched))
         h = ctypes.c_void_p()
         if isinstance(model, (bytes, bytearray)):
             buf = bytes(model)

@@ -44,6 +44,10 @@ extern "C" {
 
 typedef struct go2pi_engine go2pi_engine;
 
+/* the bits of go2pi_opts.ln_small */
+#define GO2PI_LN_SMALL 1
+#define GO2PI_LN_BATCHED 2
+
 /* Engine options. Zero-initialise, then call go2pi_default_opts(). */
 typedef struct go2pi_opts {
   int32_t struct_size;   /* = sizeof(go2pi_opts) */
@@ -69,11 +73,15 @@ typedef struct go2pi_opts {
      final layer is <= 16 wide; others keep the launch path. 0 (default): one launch
      per call. Any other call on the engine first stops the resident kernel. */
   int32_t resident_ms;
-  /* 1: a LayerNormalization policy at batch <= 8 is served like an LN-free one: by the
-     single-launch kernel and, with resident_ms > 0, by a resident kernel (go2pi_create).
-     0 (default): one launch per layer, as before this field existed. No effect on a
-     policy without LayerNormalization, on a recurrent one, or above batch 8. (The field
-     fills what was tail padding: a zero-initialised struct of the earlier layout reads 0.) */
+  /* Two bits, for a LayerNormalization policy (no effect on any other, or on a recurrent one):
+     GO2PI_LN_SMALL (1): at batch <= 8 it is served like an LN-free one: by the single-launch
+     kernel and, with resident_ms > 0, by a resident kernel (go2pi_create). Without the bit:
+     one launch per layer, as before this field existed. No effect above batch 8.
+     GO2PI_LN_BATCHED (2): above the small-batch paths, a dense LN policy whose shape the
+     4-wave pipeline serves runs on policy_mlp_ln_kernel (go2pi_create); any other keeps the
+     general batched kernel. No effect on the controller tick or at batch <= 8.
+     0 (default): neither; 3: both. Any value outside 0 .. 3 reads as 0. (The field fills what
+     was tail padding: a zero-initialised struct of the earlier layout reads 0.) */
   int32_t ln_small;
 } go2pi_opts;
 
@@ -95,7 +103,12 @@ void go2pi_default_opts(go2pi_opts *opts);
    (hidden layers 64 or 128 wide), else the multi-workgroup policy_resident_kernel (never
    policy_wide_kernel or policy_resident1_kernel). Its controller tick at batch <= 8 is the
    single launch (no resident controller form), and a recurrent LN policy keeps the
-   general body. The lean / pipeline batched kernels do not serve LN. */
+   general body. The lean / pipeline batched kernels do not serve LN; with opts.ln_small's
+   GO2PI_LN_BATCHED bit, batched launches of a dense LN policy run on the pipeline's LN kernel,
+   policy_mlp_ln_kernel<tiles per wave, head tiles>, when every hidden layer pads to the same
+   128, 256 or 512 columns with one activation, the head has at most 32 outputs (16 at 512),
+   the observation is no wider than the hidden layers, and the options add no observation
+   normalisation or clip and no action post-processing; go2pi_batched_kernel names it. */
 int go2pi_create(const char *onnx_path, const go2pi_opts *opts, go2pi_engine **out);
 int go2pi_create_from_memory(const void *onnx_bytes, size_t nbytes, const go2pi_opts *opts,
                              go2pi_engine **out);
