@@ -627,7 +627,7 @@ struct go2pi_engine {
         const bool last = l == prog.nl - 1;
         float *y = last ? act : d_tmp[l & 1];
         const int ys = last ? prog.out_dim : tmp_stride;
-        hip_check(go2pi::launch_gemv_layer(prog, l, x, xs, y, ys, (int)batch, s), "gemv_layer launch");
+        hip_check(go2pi::launch_gemv_layer(prog, l, obs, x, xs, y, ys, (int)batch, s), "gemv_layer launch");
         x = y;
         xs = ys;
       }
@@ -769,6 +769,7 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
     p.L[l].bias = e.upload(buf.bias[l]);
     p.L[l].ln_g = opt_upload(buf.ln_g[l]);
     p.L[l].ln_b = opt_upload(buf.ln_b[l]);
+    p.skip_idx[l] = buf.skip[l].empty() ? nullptr : e.upload(buf.skip[l]);  // the index table, beside the biases
   }
   const float *base = e.upload(buf.arena);
   for (int l = 0; l < p.nl; ++l) p.L[l].w = base + buf.off[l];
@@ -1226,6 +1227,11 @@ void check_ctl(const go2pi_engine *e, int64_t batch) {
   check_engine(e);
   check_batch(e, batch);
   if (!e->ctl_hist) throw ApiError("policy I/O is not a Go2 controller's (need 49*k obs, 12 actions)", GO2PI_E_MODEL);
+  // (the tick's observation is assembled in LDS and published in place; a skip layer reads
+  // the observation rows from memory)
+  if (go2pi::program_has_skip(e->prog))
+    throw ApiError("the controller tick does not serve a policy with observation skip inputs "
+                   "(assemble the observation and call go2pi_run)", GO2PI_E_INVALID);
 }
 
 // One go2pi_controller_step call: the caller's rows, their byte counts, and how they

@@ -436,6 +436,71 @@ __device__ __forceinline__ void ln_tile(const DevLayer &L, float *Y, int ys, int
   ln_rows(Y, ys, wave, GO2PI_TILE_ROWS, NW, ln_of(L), lane);
 }
 
+// A layer's observation skip input (program.hpp DevLayer::skip_n): the tile's n observation
+// columns idx[0 .. n) of this step's rows ob (global memory: layer 0 staged the same rows a
+// few microseconds earlier, so they sit in L2), through the prologue, into columns
+// [col0, col0 + n) of the 16 LDS rows the layer reads. Called after the previous layer's
+// barrier (its dense store wrote act(0) there) and its LN pass; the caller follows it with
+// one barrier. Rows over the NW waves, columns over the lanes: consecutive lanes read
+// consecutive indices, so a contiguous slice is one coalesced row segment per wave
+// instruction, and a lane reads its index and prologue constants once for all its rows.
+// Every value is the one layer 0 was given for that column (the same prologue arithmetic).
+// Rows past the batch hold 0.
+// A real call, as ln_rows is and for its reason: inlined, the pass cost the 16-wave kernel
+// (127 of 128 VGPRs) four spilled registers and 32 B of scratch per lane, and the 4- and
+// 8-wave kernels 4 VGPRs each. l: the layer that reads the columns.
+template <int NW>
+__device__ __noinline__ void skip_tile(const DevProgram &P, int l, const float *__restrict__ ob, int row0, int B,
+                                       float *Y, int ys, int wave, int lane) {
+  const Pro q = pro_of(P);
+  const int *__restrict__ idx = P.skip_idx[l];
+  const int n = P.L[l].skip_n, col0 = P.L[l - 1].N, in_dim = P.in_dim;
+  for (int j = lane; j < n; j += 64) {
+    const int c = idx[j];
+    const ProK pk = pro_k(q, c);
+    float v[(GO2PI_TILE_ROWS + NW - 1) / NW];
+#pragma unroll
+    for (int i = 0; i < (GO2PI_TILE_ROWS + NW - 1) / NW; ++i) {  // every row's load in flight before the first store
+      const int row = row0 + wave + i * NW;
+      v[i] = (wave + i * NW < GO2PI_TILE_ROWS && row < B) ? ob[(size_t)row * in_dim + c] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < (GO2PI_TILE_ROWS + NW - 1) / NW; ++i) {
+      const int r = wave + i * NW;
+      if (r < GO2PI_TILE_ROWS) Y[r * ys + col0 + j] = row0 + r < B ? prologue(q, pk, v[i]) : 0.f;
+    }
+  }
+}
+
+// bit l of the general body's skip mask (fused_body skipm); false where the body has no skip code
+template <bool SKIP>
+__device__ __forceinline__ bool skip_bit(int m, int l) {
+  if constexpr (SKIP) return (m >> l) & 1;
+  else return false;
+}
+
+// Layer 0 with a gather (DevLayer::skip_n on layer 0: it reads exactly the observation columns
+// skip_idx[0][0 .. skip_n)): the tile's staged rows X[r][k] = prologue(obs[row0 + r][idx[k]]),
+// zeros in the padding columns [skip_n, in_pad) and in rows past the batch. One element per
+// thread and round, consecutive threads on consecutive k. A column the layer does not read is
+// never loaded, so a non-finite value in it cannot reach the layer (0 * inf is NaN: zero
+// weight columns would not do). A call, for skip_tile's reason.
+inline __device__ __noinline__ void gather_stage(const DevProgram &P, const float *__restrict__ ob, int row0, int B,
+                                                 float *X, int xs, int tid, int nt) {
+  const Pro q = pro_of(P);
+  const int *__restrict__ idx = P.skip_idx[0];
+  const int n = P.L[0].skip_n, in_pad = P.in_pad, in_dim = P.in_dim;
+  for (int e = tid; e < GO2PI_TILE_ROWS * in_pad; e += nt) {
+    const int r = e / in_pad, k = e - r * in_pad, row = row0 + r;
+    float v = 0.f;
+    if (row < B && k < n) {
+      const int c = idx[k];
+      v = prologue(q, ob[(size_t)row * in_dim + c], c);
+    }
+    X[r * xs + k] = v;
+  }
+}
+
 // GRU cell (ONNX semantics, linear_before_reset = 1) for one 16-robot tile.
 // X: LDS rows [16][xs] holding x in columns [0, I_pad); Hs: LDS hidden rows
 // (stride xs). Writes h' to Y[:, 0:H]; the caller copies it back into Hs after
@@ -1996,13 +2061,22 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
   // Touch every layer descriptor up front: one burst of scalar loads warms the
   // scalar cache, so each layer's start does not pay a K$ miss on its fields
   // (measured: layer entry ~990 -> ~740 cycles after the barrier).
+  // (the general body only) observation skip inputs: skip_tile behind a layer whose
+  // consumer has one, gather_stage where layer 0 itself reads a gather (DevLayer::skip_n).
+  // skipm, bit l: layer l has one; read here with the descriptors, so the test behind each
+  // layer's barrier is scalar arithmetic and waits for no load
+  constexpr bool SKIP = W4T == 0 && !CTL && RNN == 0;
+  int skipm = 0;
   if constexpr (W4T > 0) {
     // pipeline: no warm-up (holding every descriptor in SGPRs spilled them to VGPR
     // lanes; the fields are read where needed and hit the scalar cache after the
     // first layer)
   } else {
     int d = 0;
-    for (int l = 0; l < P.nl; ++l) d ^= P.L[l].K_pad ^ P.L[l].N_pad ^ P.L[l].act ^ (int)(size_t)P.L[l].w;
+    for (int l = 0; l < P.nl; ++l) {
+      d ^= P.L[l].K_pad ^ P.L[l].N_pad ^ P.L[l].act ^ (int)(size_t)P.L[l].w;
+      if constexpr (SKIP) skipm |= (P.L[l].skip_n != 0) << l;
+    }
     asm volatile("" ::"s"(d));  // consumes the loads; no side effect
   }
   // init sub-phases: 40 descriptors warm, 41 observation loads issued, 42 pipeline barrier reached
@@ -2040,7 +2114,9 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
   }
   // plain observation rows with no prologue arithmetic are staged by direct-to-LDS
   // loads (needs whole 64-column chunks to fit the LDS row)
-  const bool glds_obs = !CTL && !P.pre_sub && !P.pre_div && !P.pre_mul && !P.pre_clip && ((P.in_pad + 63) & ~63) <= S;
+  // (a layer-0 gather has no direct-to-LDS form: gather_stage, in the plain branch below)
+  const bool glds_obs = !CTL && !P.pre_sub && !P.pre_div && !P.pre_mul && !P.pre_clip &&
+                        ((P.in_pad + 63) & ~63) <= S && !skip_bit<SKIP>(skipm, 0);
   auto stage_obs = [&](int step) {
     if constexpr (CTL) {  // this tile's rows of ctl.obs are read only from the LDS image: publish in place
       if (ctl_late) return;  // (w4_step)
@@ -2075,6 +2151,12 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
       }
     } else {
       const float *ob = obs + (size_t)step * B * P.in_dim;
+      if constexpr (SKIP) {
+        if (skipm & 1) {  // uniform over the workgroup
+          gather_stage(P, ob, row0, B, bufA, S, tid, NT);
+          return;
+        }
+      }
       for (int e = tid; e < GO2PI_TILE_ROWS * P.in_pad; e += NT) {
         const int r = e / P.in_pad, k = e - r * P.in_pad, row = row0 + r;
         float v = 0.f;
@@ -2238,6 +2320,13 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
       if constexpr (W4T == 0) {
         if (P.L[l].ln) {  // uniform over the workgroup: every wave reaches the barrier below
           ln_tile<NW>(P.L[l], Y, S, wave, lane);
+          __syncthreads();
+        }
+      }
+      // the next layer's observation skip input, behind this layer's store and LN pass
+      if constexpr (SKIP) {
+        if ((skipm >> (l + 1)) & 1) {  // uniform over the workgroup (no bit past the last layer)
+          skip_tile<NW>(P, l + 1, obs + (size_t)step * B * P.in_dim, row0, B, Y, S, wave, lane);
           __syncthreads();
         }
       }

@@ -36,12 +36,20 @@ namespace go2pi {
 // y: [B][y_stride]. Layer 0 applies the prologue; the final layer the epilogue.
 constexpr int GEMV_WAVES = lds::WAVES;
 
-__global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram P, int layer, const float *x,
-                                                                     int x_stride, float *y, int y_stride, int B) {
+// obs: the call's observation rows [B][in_dim] (the engine's staging buffer in a captured
+// graph: every replay reads the fresh rows), read by a layer with an observation skip input
+// (DevLayer::skip_n): its staged row is [the previous layer's N outputs | obs columns
+// skip_idx[0 .. skip_n) through the prologue], and layer 0's a gather of those columns.
+__global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram P, int layer, const float *obs,
+                                                                     const float *x, int x_stride, float *y,
+                                                                     int y_stride, int B) {
   extern __shared__ float4 lds4[];
   const DevLayer &L = P.L[layer];
   const int K_pad = L.K_pad, C = K_pad >> 4, T = L.N_pad >> 4;
-  const int K = layer == 0 ? P.in_dim : P.L[layer - 1].N;
+  const int skip_n = L.skip_n;
+  const int *sidx = P.skip_idx[layer];
+  // the columns read from x (layer 0 with a gather: none, all of its columns come through sidx)
+  const int K = layer == 0 ? (skip_n ? 0 : P.in_dim) : P.L[layer - 1].N;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int t = blockIdx.x;
@@ -64,6 +72,10 @@ __global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram 
     if (k < K) {
       v = x[(size_t)b * x_stride + k];
       if (layer == 0) v = prologue(P, v, k);
+    } else if (k < K + skip_n) {
+      // (the LN pass below normalises columns [0, K) by index and leaves these as they are)
+      const int c = sidx[k - K];
+      v = prologue(P, obs[(size_t)b * P.in_dim + c], c);
     }
     xs[b * K_pad + k] = v;
   }
@@ -492,13 +504,13 @@ int launch_policy_fused_ctl(const DevProgram &p, const DevProgram *p_dev, int wa
   });
 }
 
-int launch_gemv_layer(const DevProgram &p, int layer, const float *x, int x_stride, float *y, int y_stride,
-                      int batch, void *stream) {
+int launch_gemv_layer(const DevProgram &p, int layer, const float *obs, const float *x, int x_stride, float *y,
+                      int y_stride, int batch, void *stream) {
   if (batch <= 0) return 0;
   if (batch > GO2PI_SMALL_MAXB) return (int)hipErrorInvalidValue;
   const dim3 grid(p.L[layer].N_pad >> 4);
   hipLaunchKernelGGL(gemv_layer_kernel, grid, dim3(GEMV_WAVES * 64), sizeof(float) * gemv_lds_of(p, layer).total,
-                     reinterpret_cast<hipStream_t>(stream), p, layer, x, x_stride, y, y_stride, batch);
+                     reinterpret_cast<hipStream_t>(stream), p, layer, obs, x, x_stride, y, y_stride, batch);
   return (int)hipGetLastError();
 }
 

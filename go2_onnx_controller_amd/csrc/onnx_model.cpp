@@ -308,6 +308,120 @@ std::vector<int64_t> ints_of(const std::unordered_map<std::string, Tensor> &init
   return it->second.i;
 }
 
+// The columns [b, e) a Slice takes of a [batch, F] value: opset 10+ inputs or opset 1-9
+// attributes, negative and out-of-range bounds clamped as ONNX defines. A step other than
+// 1, the batch axis, and an empty result are refused.
+struct Cols {
+  int64_t b = 0, e = 0;
+};
+
+Cols slice_cols(const Node &sl, const std::unordered_map<std::string, Tensor> &inits, int64_t F) {
+  std::vector<int64_t> st, en, ax, sp;
+  if (sl.in.size() > 1) {
+    st = ints_of(inits, sl, 1);
+    en = ints_of(inits, sl, 2);
+    ax = ints_of(inits, sl, 3);
+    sp = ints_of(inits, sl, 4);
+  } else {  // opset 1-9: attributes
+    auto a = sl.attrs.find("starts"), b = sl.attrs.find("ends"), c = sl.attrs.find("axes");
+    if (a == sl.attrs.end() || b == sl.attrs.end()) fail("Slice without starts / ends");
+    st = a->second.ints;
+    en = b->second.ints;
+    if (c != sl.attrs.end()) ax = c->second.ints;
+  }
+  if (ax.empty())
+    for (size_t i = 0; i < st.size(); ++i) ax.push_back((int64_t)i);
+  if (st.size() != en.size() || ax.size() != st.size() || (!sp.empty() && sp.size() != st.size()))
+    fail("Slice: starts / ends / axes / steps lengths differ");
+  Cols bl{0, F};
+  for (size_t i = 0; i < st.size(); ++i) {
+    const int64_t a = ax[i] < 0 ? ax[i] + 2 : ax[i];
+    if (!sp.empty() && sp[i] != 1) fail("Slice with a step other than 1 is unsupported");
+    auto clampi = [&](int64_t v, int64_t dim) { return std::max<int64_t>(0, std::min(v < 0 ? v + dim : v, dim)); };
+    if (a == 0) {
+      if (clampi(st[i], INT64_MAX) != 0 || en[i] < INT32_MAX) fail("Slice on the batch axis is unsupported");
+    } else if (a == 1) {
+      bl.b = clampi(st[i], F);
+      bl.e = clampi(en[i], F);
+    } else {
+      fail("Slice axis out of range for a [batch, features] observation");
+    }
+  }
+  if (bl.e <= bl.b) fail("empty Slice of the observation");
+  return bl;
+}
+
+struct GraphView {
+  const std::vector<Node> &nodes;
+  const std::unordered_map<std::string, Tensor> &inits;
+  const std::unordered_map<std::string, std::vector<size_t>> &consumers;
+  const std::unordered_map<std::string, size_t> &producers;
+  const std::string &obs;  // graph input 0
+
+  // v is computed from the observation alone: obs through Slice / Identity and
+  // Sub / Div / Mul / Clip by constants (a front-end block, a prologue value, a skip part)
+  bool obs_derived(std::string v) const {
+    for (int hop = 0; hop < 64; ++hop) {
+      if (v == obs) return true;
+      auto p = producers.find(v);
+      if (p == producers.end()) return false;
+      const Node &nd = nodes[p->second];
+      if (nd.in.empty()) return false;
+      if (nd.op == "Slice" || nd.op == "Identity" || nd.op == "Clip") {
+        v = nd.in[0];
+      } else if (nd.op == "Sub" || nd.op == "Div" || nd.op == "Mul") {
+        if (nd.in.size() < 2) return false;
+        const bool c0 = inits.count(nd.in[0]) > 0, c1 = inits.count(nd.in[1]) > 0;
+        if (c0 == c1) return false;
+        v = c0 ? nd.in[1] : nd.in[0];
+      } else {
+        return false;
+      }
+    }
+    return false;
+  }
+  // v, through Slice / Identity alone, reaches a Concat
+  bool to_concat(const std::string &v, int depth = 0) const {
+    auto it = consumers.find(v);
+    if (it == consumers.end() || depth > 16) return false;
+    for (size_t c : it->second)
+      if (node_to_concat(c, depth)) return true;
+    return false;
+  }
+  bool node_to_concat(size_t c, int depth = 0) const {
+    const Node &nd = nodes[c];
+    if (nd.op == "Concat") return true;
+    return (nd.op == "Slice" || nd.op == "Identity") && !nd.out.empty() && to_concat(nd.out[0], depth + 1);
+  }
+  // A Slice of the observation (its output v) that is no front-end block: its chain
+  // feeds a Gemm / MatMul (layer 0 reads a slice) or a Concat that also
+  // takes a value not computed from the observation alone (a skip Concat). A front-end
+  // Concat takes observation blocks only.
+  bool skip_slice(const std::string &v, int depth = 0) const {
+    auto it = consumers.find(v);
+    if (it == consumers.end() || depth > 16) return false;
+    for (size_t c : it->second) {
+      const Node &nd = nodes[c];
+      if (nd.op == "Gemm" || nd.op == "MatMul") {
+        if (!nd.in.empty() && nd.in[0] == v) return true;
+      } else if (nd.op == "Concat") {
+        for (auto &in : nd.in)
+          if (!obs_derived(in)) return true;
+      } else if ((nd.op == "Slice" || nd.op == "Identity" || nd.op == "Sub" || nd.op == "Div" || nd.op == "Mul" ||
+                  nd.op == "Clip") &&
+                 !nd.out.empty()) {
+        // (arithmetic on the way too: where the chain ends decides, and the walker refuses it)
+        if (skip_slice(nd.out[0], depth + 1)) return true;
+      }
+    }
+    return false;
+  }
+};
+
+const char *const kPartArith =
+    "an observation part of a skip Concat must be taken from the value layer 0 reads (the observation after "
+    "its prologue / front-end), with no arithmetic of its own";
+
 // The per-block observation front-end: the observation Sliced into column blocks,
 // each block through its own Sub / Div / Mul / Clip, then Concatenated on the feature
 // axis (e.g. per-block normalisation of a controller's history blocks, controller.hpp
@@ -319,14 +433,21 @@ std::vector<int64_t> ints_of(const std::unordered_map<std::string, Tensor> &init
 // is. (The reference hands any graph to onnxruntime, onnx_actor.cpp:16; a front-end
 // this cannot lower exactly is refused, never approximated.)
 void front_end(Model &m, const std::vector<Node> &nodes, const std::unordered_map<std::string, Tensor> &inits,
-               const std::unordered_map<std::string, std::vector<size_t>> &consumers, std::vector<bool> &used,
-               std::string &cur) {
+               const std::unordered_map<std::string, std::vector<size_t>> &consumers, const GraphView &gv,
+               std::vector<bool> &used, std::string &cur) {
   const std::string obs = m.inputs[0].name;
   auto ci = consumers.find(obs);
   if (ci == consumers.end()) return;
-  bool any_slice = false;
-  for (size_t k : ci->second) any_slice |= nodes[k].op == "Slice";
-  if (!any_slice) return;
+  // Slices that are skip parts or layer 0's own input are the walker's (parse_onnx), not a
+  // front-end; a graph input with both kinds has parts that skipped the front-end's arithmetic
+  size_t n_slice = 0, n_skip = 0;
+  for (size_t k : ci->second)
+    if (nodes[k].op == "Slice" && !nodes[k].out.empty()) {
+      ++n_slice;
+      n_skip += gv.skip_slice(nodes[k].out[0]) ? 1 : 0;
+    }
+  if (n_slice == 0 || n_skip == n_slice) return;
+  if (n_skip) fail(kPartArith);
   const auto &shape = m.inputs[0].shape;
   if (shape.size() != 2 || shape[1] <= 0) fail("Slice on the observation needs a static [batch, features] input shape");
   const int64_t F = shape[1];
@@ -356,40 +477,12 @@ void front_end(Model &m, const std::vector<Node> &nodes, const std::unordered_ma
   for (size_t k : ci->second) {
     const Node &sl = nodes[k];
     if (sl.op != "Slice" || sl.in.at(0) != obs) fail("the observation feeds a Slice front-end and a '" + sl.op + "'");
-    std::vector<int64_t> st, en, ax, sp;
-    if (sl.in.size() > 1) {
-      st = ints_of(inits, sl, 1);
-      en = ints_of(inits, sl, 2);
-      ax = ints_of(inits, sl, 3);
-      sp = ints_of(inits, sl, 4);
-    } else {  // opset 1-9: attributes
-      auto a = sl.attrs.find("starts"), b = sl.attrs.find("ends"), c = sl.attrs.find("axes");
-      if (a == sl.attrs.end() || b == sl.attrs.end()) fail("Slice without starts / ends");
-      st = a->second.ints;
-      en = b->second.ints;
-      if (c != sl.attrs.end()) ax = c->second.ints;
-    }
-    if (ax.empty())
-      for (size_t i = 0; i < st.size(); ++i) ax.push_back((int64_t)i);
-    if (st.size() != en.size() || ax.size() != st.size() || (!sp.empty() && sp.size() != st.size()))
-      fail("Slice: starts / ends / axes / steps lengths differ");
     Block bl;
-    bl.b = 0;
-    bl.e = F;
-    for (size_t i = 0; i < st.size(); ++i) {
-      const int64_t a = ax[i] < 0 ? ax[i] + 2 : ax[i];
-      if (!sp.empty() && sp[i] != 1) fail("Slice with a step other than 1 is unsupported");
-      auto clampi = [&](int64_t v, int64_t dim) { return std::max<int64_t>(0, std::min(v < 0 ? v + dim : v, dim)); };
-      if (a == 0) {
-        if (clampi(st[i], INT64_MAX) != 0 || en[i] < INT32_MAX) fail("Slice on the batch axis is unsupported");
-      } else if (a == 1) {
-        bl.b = clampi(st[i], F);
-        bl.e = clampi(en[i], F);
-      } else {
-        fail("Slice axis out of range for a [batch, features] observation");
-      }
+    {
+      const Cols c = slice_cols(sl, inits, F);
+      bl.b = c.b;
+      bl.e = c.e;
     }
-    if (bl.e <= bl.b) fail("empty Slice of the observation");
     used[k] = true;
     const int64_t w = bl.e - bl.b;
     auto per_col = [&](const Tensor &C, const std::string &what) {
@@ -572,10 +665,69 @@ Model parse_onnx(const uint8_t *data, size_t n) {
     for (auto &in : nodes[i].in)
       if (!in.empty()) consumers[in].push_back(i);
 
-  // Walk the single-consumer chain from input 0 to output 0.
+  std::unordered_map<std::string, size_t> producers;
+  for (size_t i = 0; i < nodes.size(); ++i)
+    for (auto &o : nodes[i].out)
+      if (!o.empty()) producers.emplace(o, i);
+  const GraphView gv{nodes, inits, consumers, producers, m.inputs[0].name};
+
+  // Walk the main chain from input 0 to output 0: every value has one consumer, except the
+  // observation as layer 0 reads it (x0), which skip Concats further down may read too.
   std::string cur = m.inputs[0].name;
   std::vector<bool> used(nodes.size(), false);
-  front_end(m, nodes, inits, consumers, used, cur);
+  front_end(m, nodes, inits, consumers, gv, used, cur);
+  // Observation skip inputs (onnx_model.hpp Dense::skip). x0: the value layer 0 reads, named
+  // through any Identity in front of it; x0_width: its columns. l0_*: layer 0 reads a Slice
+  // of x0 (a gather: a column it does not read is never multiplied, so a non-finite value
+  // there cannot reach it). pend: a resolved skip Concat waiting for its Gemm / MatMul.
+  std::string x0;
+  int64_t x0_width = 0;
+  bool l0_sliced = false;
+  Cols l0_cols;
+  struct {
+    bool on = false;
+    int nrun = 0;                // the running value's width
+    std::vector<int> perm, skip;  // device column j <- ONNX column perm[j]; x0 column of device column nrun + j
+  } pend;
+  auto canon = [&](std::string v) {  // v's name in front of any Identity
+    for (int hop = 0; hop < 64; ++hop) {
+      auto pi = producers.find(v);
+      if (pi == producers.end() || nodes[pi->second].op != "Identity" || nodes[pi->second].in.empty()) break;
+      v = nodes[pi->second].in[0];
+    }
+    return v;
+  };
+  // A skip Concat's input that is not the running value: the columns of x0 it holds. It is
+  // x0 itself or a Slice of it (Slices of Slices compose), Identity anywhere.
+  auto resolve_part = [&](const std::string &name) -> Cols {
+    std::vector<size_t> slices;  // outermost first
+    std::string v = name;
+    for (int hop = 0;; ++hop) {
+      if (v == x0) break;
+      if (hop >= 64) fail("Concat input '" + name + "' is too deep a chain");
+      auto pi = producers.find(v);
+      if (pi == producers.end()) {
+        if (v == m.inputs[0].name) fail(kPartArith);
+        fail("Concat input '" + v + "' is neither the running value nor a part of the observation");
+      }
+      const Node &pn = nodes[pi->second];
+      if (pn.in.empty()) fail("Concat input '" + v + "' is neither the running value nor a part of the observation");
+      if (pn.op == "Slice") slices.push_back(pi->second);
+      else if (pn.op != "Identity") {
+        if (gv.obs_derived(v)) fail(kPartArith);
+        fail("a Concat of two running values (two sub-networks joined) is unsupported (input '" + v + "' comes from '" +
+             pn.op + "')");
+      }
+      used[pi->second] = true;
+      v = pn.in[0];
+    }
+    Cols c{0, x0_width};
+    for (size_t i = slices.size(); i-- > 0;) {
+      const Cols r = slice_cols(nodes[slices[i]], inits, c.e - c.b);
+      c = Cols{c.b + r.b, c.b + r.e};
+    }
+    return c;
+  };
   bool last_has_act = true;  // true => next Add cannot fold into a bias
   bool pending_bias_ok = false;
   // elementwise ops after the last layer's activation: a Mul by a constant is held
@@ -601,19 +753,52 @@ Model parse_onnx(const uint8_t *data, size_t n) {
   // except a held column scale, folded into its weights here
   auto begin_layer = [&](Dense &d, const std::string &op) {
     if (post_clip) fail(op + ": a Clip after an activation is only supported at the end of the graph");
-    if (!col_scale.empty()) {
-      if ((int)col_scale.size() != 1 && (int)col_scale.size() != d.K) fail(op + ": the Mul before it must broadcast over K");
+    int nrun = d.K;  // the columns that read the previous layer's outputs
+    if (pend.on) {
+      // the skip Concat in front: W's columns into device order (running value first, then
+      // the observation parts in Concat order)
+      if (d.K != (int)pend.perm.size())
+        fail(op + ": K = " + std::to_string(d.K) + " does not match its skip Concat's " +
+             std::to_string(pend.perm.size()) + " columns");
+      std::vector<float> W(d.W.size());
       for (int i = 0; i < d.N; ++i)
-        for (int k = 0; k < d.K; ++k) d.W[size_t(i) * d.K + k] *= col_scale[col_scale.size() == 1 ? 0 : k];
+        for (int k = 0; k < d.K; ++k) W[size_t(i) * d.K + k] = d.W[size_t(i) * d.K + pend.perm[k]];
+      d.W = std::move(W);
+      d.skip = std::move(pend.skip);
+      nrun = pend.nrun;
+      pend = {};
+    } else if (m.layers.empty() && !m.has_gru) {
+      if (l0_sliced) {  // layer 0 reads a Slice of x0: a gather
+        if (d.K != l0_cols.e - l0_cols.b)
+          fail(op + ": K = " + std::to_string(d.K) + " does not match the Slice of the observation it reads");
+        for (int64_t c = l0_cols.b; c < l0_cols.e; ++c) d.skip.push_back((int)c);
+      } else {
+        x0 = canon(cur);
+        x0_width = d.K;
+      }
+    }
+    if (!col_scale.empty()) {
+      // (a held scale applies to the running value's columns, not to the observation parts)
+      if ((int)col_scale.size() != 1 && (int)col_scale.size() != nrun) fail(op + ": the Mul before it must broadcast over K");
+      for (int i = 0; i < d.N; ++i)
+        for (int k = 0; k < nrun; ++k) d.W[size_t(i) * d.K + k] *= col_scale[col_scale.size() == 1 ? 0 : k];
       col_scale.clear();
     }
   };
   while (cur != final_out) {
     auto it = consumers.find(cur);
-    size_t idx = SIZE_MAX;
+    size_t idx = SIZE_MAX, n_unused = 0;
     if (it != consumers.end())
       for (size_t k : it->second)
-        if (!used[k]) { idx = k; break; }
+        if (!used[k]) {
+          if (idx == SIZE_MAX) idx = k;
+          ++n_unused;
+        }
+    // the observation with skip branches: the main chain is the consumer that does not
+    // lead, through Slice / Identity alone, to a Concat
+    if (n_unused > 1)
+      for (size_t k : it->second)
+        if (!used[k] && !gv.node_to_concat(k)) { idx = k; break; }
     if (idx == SIZE_MAX) fail("dangling value '" + cur + "' does not reach output '" + final_out + "'");
     used[idx] = true;
     const Node &nd = nodes[idx];
@@ -622,6 +807,11 @@ Model parse_onnx(const uint8_t *data, size_t n) {
       return nd.in[0] == cur ? nd.in[1] : nd.in[0];
     };
     const bool at_input = m.layers.empty() && !m.has_gru;  // still in front of the first layer
+    const bool linear = nd.op == "Gemm" || nd.op == "MatMul";
+    if (pend.on && !linear && nd.op != "Identity")
+      fail("a skip Concat must feed a Gemm or MatMul: '" + nd.op + "' applied to the concatenation is unsupported");
+    if (l0_sliced && at_input && !linear && nd.op != "Identity")
+      fail("a Slice of the observation in front of the first layer must feed a Gemm or MatMul, not '" + nd.op + "'");
 
     if (nd.op == "Gemm") {
       if (nd.in[0] != cur) fail("Gemm: activation must be input A");
@@ -711,6 +901,53 @@ Model parse_onnx(const uint8_t *data, size_t n) {
       Dense &d = m.layers.back();
       if (C.numel() != d.N && C.numel() != 1) fail("Add: bias must broadcast over N");
       for (int i = 0; i < d.N; ++i) d.b[i] += C.numel() == 1 ? C.f[0] : C.f[i];
+    } else if (nd.op == "Add" && nd.in.size() >= 2) {
+      fail("Add of two computed values (a residual connection) is unsupported (node '" + nd.name + "')");
+    } else if (nd.op == "Slice") {
+      // layer 0 reads a Slice of the observation (an encoder that reads part of it)
+      if (!at_input || nd.in.at(0) != cur)
+        fail("Slice is only supported on the observation (a front-end block, a skip part or layer 0's input)");
+      const auto &shape = m.inputs[0].shape;
+      if (shape.size() != 2 || shape[1] <= 0 || shape[1] > INT32_MAX / 2)
+        fail("Slice on the observation needs a static [batch, features] input shape");
+      x0 = canon(cur);
+      x0_width = shape[1];
+      l0_cols = slice_cols(nd, inits, x0_width);
+      l0_sliced = true;
+    } else if (nd.op == "Concat") {
+      // a skip Concat: the running value and one or more parts of x0, on the feature axis
+      if (m.has_gru) fail("a skip Concat in a policy with a GRU or LSTM cell is unsupported");
+      if (at_input)
+        fail("a Concat of observation parts alone in front of the first layer is a front-end, not a skip input "
+             "(node '" + nd.name + "')");
+      const int64_t axis = nd.iattr("axis", 1);
+      if (axis != 1 && axis != -1)
+        fail("a skip Concat must be on the feature axis (1 or -1), not axis " + std::to_string(axis));
+      if (post_clip) fail("Concat: a Clip after an activation is only supported at the end of the graph");
+      const int prevN = m.layers.back().N;
+      int64_t at = 0, run_at = -1;
+      std::vector<std::pair<int64_t, Cols>> parts;  // ONNX column offset, x0 columns
+      for (auto &name : nd.in) {
+        if (name == cur) {
+          if (run_at >= 0) fail("a skip Concat takes the running value twice");
+          run_at = at;
+          at += prevN;
+        } else {
+          const Cols c = resolve_part(name);
+          parts.emplace_back(at, c);
+          at += c.e - c.b;
+        }
+      }
+      if (parts.empty() || run_at < 0) fail("a skip Concat needs the running value and at least one observation part");
+      if (at > INT32_MAX / 2) fail("a skip Concat is too wide");
+      pend.on = true;
+      pend.nrun = prevN;
+      for (int j = 0; j < prevN; ++j) pend.perm.push_back((int)run_at + j);
+      for (auto &pc : parts)
+        for (int64_t c = pc.second.b; c < pc.second.e; ++c) {
+          pend.perm.push_back((int)(pc.first + (c - pc.second.b)));
+          pend.skip.push_back((int)c);
+        }
     } else if ((nd.op == "Sub" || nd.op == "Div") && at_input && nd.in[0] == cur && is_init(other_input())) {
       // observation normalisation, evaluated as written: (x - sub) / div
       const Tensor &C = init(other_input());
@@ -847,6 +1084,7 @@ Model parse_onnx(const uint8_t *data, size_t n) {
     cur = nd.out[0];
   }
 
+  if (pend.on) fail("a skip Concat must feed a Gemm or MatMul: it is the graph's output");
   if (m.layers.empty()) fail("policy has no linear layer");
   if (m.layers.back().ln) fail("LayerNormalization on the output layer is unsupported");
   if (rnn_node != SIZE_MAX) {
@@ -920,11 +1158,17 @@ Model parse_onnx(const uint8_t *data, size_t n) {
     if (col_scale.size() != 1) fail("a per-feature Mul after the final activation is unsupported");
     m.post_scale = col_scale[0];
   }
-  const int first_in = m.has_gru ? m.gru.I : m.layers[0].K;
+  const int first_in = m.has_gru ? m.gru.I : l0_sliced ? (int)x0_width : m.layers[0].K;
   m.in_dim = first_in;
   if (m.has_gru && m.layers[0].K != m.gru.H) fail("recurrent hidden size does not match the first dense layer");
   for (size_t l = 1; l < m.layers.size(); ++l)
-    if (m.layers[l].K != m.layers[l - 1].N) fail("layer " + std::to_string(l) + " input dim mismatch");
+    if (m.layers[l].K != m.layers[l - 1].N + (int)m.layers[l].skip.size())
+      fail("layer " + std::to_string(l) + " input dim mismatch");
+  for (auto &d : m.layers) {
+    if (m.has_gru && !d.skip.empty()) fail("a skip input in a policy with a GRU or LSTM cell is unsupported");
+    for (int c : d.skip)
+      if (c < 0 || c >= m.in_dim) fail("a skip input reads a column outside the observation");
+  }
   m.out_dim = m.layers.back().N;
   if (!m.pre_sub.empty() && int(m.pre_sub.size()) != m.in_dim && m.pre_sub.size() != 1) fail("prologue Sub size");
   if (!m.pre_div.empty() && int(m.pre_div.size()) != m.in_dim && m.pre_div.size() != 1) fail("prologue Div size");
@@ -993,7 +1237,9 @@ std::string inspect_json(const Model &m) {
          ",\"act\":" + std::to_string(d.act) + ",\"alpha\":" + json_num(d.alpha) + ",\"beta\":" + json_num(d.beta) +
          ",\"w_sum\":" + json_num(sum_of(d.W)) + ",\"b_sum\":" + json_num(sum_of(d.b)) +
          ",\"ln\":" + std::to_string(d.ln) + ",\"ln_eps\":" + json_num(d.ln_eps) +
-         ",\"ln_g_sum\":" + json_num(sum_of(d.ln_g)) + ",\"ln_b_sum\":" + json_num(sum_of(d.ln_b)) + "}";
+         ",\"ln_g_sum\":" + json_num(sum_of(d.ln_g)) + ",\"ln_b_sum\":" + json_num(sum_of(d.ln_b)) + ",\"skip\":[";
+    for (size_t i = 0; i < d.skip.size(); ++i) j += (i ? "," : "") + std::to_string(d.skip[i]);
+    j += "]}";
   }
   j += "],\"gru\":";
   if (m.has_gru)

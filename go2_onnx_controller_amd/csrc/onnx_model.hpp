@@ -1,6 +1,7 @@
 // ONNX policy loader: a minimal protobuf reader plus a pattern matcher that
 // lowers an exported policy graph to the engine's program (dense layers with a
-// fused activation and an optional LayerNormalization, optional leading GRU,
+// fused activation, an optional LayerNormalization and an optional observation skip input
+// (Concat of the previous layer's value and Slices of the observation), optional leading GRU,
 // optional affine prologue and clip epilogue). Replaces what the reference gets from onnxruntime's session
 // creation (onnx_inference/src/cpp/onnx_actor.cpp:16, :23-28).
 #pragma once
@@ -33,6 +34,12 @@ struct Dense {
   int ln = 0;
   float ln_eps = 1e-5f;
   std::vector<float> ln_g, ln_b;  // Scale, B: [N] each (B zeros when the node has none)
+  // Observation skip input: columns of x0 (the value layer 0 reads: the graph input after
+  // its prologue / front-end) appended to this layer's input, which is then
+  // [the previous layer's N outputs | x0[skip[0]], x0[skip[1]], ...], K = prev.N + skip.size();
+  // W's columns are in that (device) order. On layer 0, which has no previous layer, a
+  // non-empty skip is a gather: the layer reads exactly these columns of x0. Empty: none.
+  std::vector<int> skip;
 };
 
 // ONNX GRU (opset 14), forward, layout 0, one layer; gates ordered z, r, h.

@@ -16,10 +16,13 @@ inline int ceil64(int x) { return (x + 63) & ~63; }
 
 // K is padded to a multiple of 64 (4 chunks: the kernel's unroll); a hidden layer's
 // N to its consumer's K_pad (64), the final layer's N to 16 (one MFMA tile).
+// next_k: the consumer's K where it has a skip input (its K_pad = ceil64(N + skip_n) can pass
+// ceil64(N): the extra tiles are zero weights and biases, and the consumer's skip columns
+// overwrite part of what their store leaves), else 0.
 void pack_dense(const Dense &d, bool last, std::vector<float> &w, std::vector<float> &b, int &K_pad, int &N_pad,
-                int kq = 64) {
+                int kq = 64, int next_k = 0) {
   K_pad = kq == 16 ? ceil16(d.K) : ceil64(d.K);
-  N_pad = last ? ceil16(d.N) : ceil64(d.N);
+  N_pad = last ? ceil16(d.N) : ceil64(std::max(d.N, next_k));
   const int T = N_pad / 16, C = K_pad / 16;
   w.assign((size_t)T * C * 64 * 4, 0.f);
   for (int t = 0; t < T; ++t)
@@ -86,6 +89,9 @@ int w4_shape_tpw(const Model &m) {
 // policy_act1_kernel's act() form or the multi-workgroup kernel.
 bool w4_eligible(const Model &m, const go2pi_opts &o, const Switches &sw, bool ln) {
   const int nl = (int)m.layers.size();
+  // an observation skip input: the general body and the GEMV chain only
+  for (const auto &d : m.layers)
+    if (!d.skip.empty()) return false;
   if (!(o.waves == 0 || o.waves == 4) || nl < 2) return false;
   if (m.has_gru && m.gru.H % 64) return false;
   if (m.has_gru && m.gru.cell == 0 && m.gru.lbr == 0) return false;  // the two-pass cell: generic body only
@@ -169,6 +175,8 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
     const auto &d = m.layers[l];
     auto &L = p.L[l];
     L.N = d.N;
+    L.skip_n = (int)d.skip.size();
+    buf.skip[l] = d.skip;
     L.act = d.act;
     L.alpha = d.alpha;
     L.beta = d.beta;
@@ -190,6 +198,10 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
     wbytes += 4.0 * ((double)d.K * d.N + d.N);
   }
   pl.has_ln = program_has_ln(p);
+  // An observation skip input on any layer: the program runs on the general batched body and
+  // the GEMV chain alone: no pipeline (w4_eligible), LN pipeline, single launch or resident
+  // form below, and no controller tick (the engine refuses it).
+  pl.has_skip = program_has_skip(p);
   // The 4-wave pipeline (decided below) takes a layer 0 of 3 (mod 4) k-chunks:
   // a 48- or 98-wide observation is padded to 16 columns, not 64 (25 % / 12.5 %
   // fewer layer-0 MFMAs and fragment bytes). Other kernels take any chunk count.
@@ -204,7 +216,8 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
     const auto &d = m.layers[l];
     auto &L = p.L[l];
     std::vector<float> w;
-    pack_dense(d, l == p.nl - 1, w, buf.bias[l], L.K_pad, L.N_pad, l == 0 ? k0q : 64);
+    const int next_k = (l + 1 < p.nl && !m.layers[l + 1].skip.empty()) ? m.layers[l + 1].K : 0;
+    pack_dense(d, l == p.nl - 1, w, buf.bias[l], L.K_pad, L.N_pad, l == 0 ? k0q : 64, next_k);
     buf.off[l] = buf.arena.size();
     buf.arena.insert(buf.arena.end(), w.begin(), w.end());
     if (d.ln) {  // scale and bias padded to N_pad with zeros
@@ -256,7 +269,8 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   if (p.nl >= 2 && !sw.no_head_fuse) {  // (the switch: A/B diagnostics only)
     const int t_last = p.L[p.nl - 1].N_pad / 16, t_prev = p.L[p.nl - 2].N_pad / 16;
     // (not behind a LayerNormalization: dense_layer_head feeds the head from un-normalised registers)
-    if (t_last <= 2 && t_prev >= pl.waves && !p.L[p.nl - 2].ln) p.head_fuse = t_last;
+    // (nor a head with a skip input: its observation columns are not in those registers)
+    if (t_last <= 2 && t_prev >= pl.waves && !p.L[p.nl - 2].ln && !p.L[p.nl - 1].skip_n) p.head_fuse = t_last;
   }
   // 4-wave uniform-MLP pipeline (kernels.hip, w4_step): a fused head, and
   // every hidden layer exactly one group of 2, 4 or 8 tiles per wave. It is the
@@ -334,13 +348,13 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
                      !sw.small_chain;  // (the switch: diagnostics, force the GEMV chain)
   // (a LayerNormalization policy: only with opts.ln_small's GO2PI_LN_SMALL bit, ln_bits;
   // latency_body normalises the swept rows as gemv_layer_kernel does)
-  pl.latency_ok = !m.has_gru && pl.latency_shape && (!pl.has_ln || (ln_bits(o) & GO2PI_LN_SMALL));
+  pl.latency_ok = !m.has_gru && pl.latency_shape && (!pl.has_ln || (ln_bits(o) & GO2PI_LN_SMALL)) && !pl.has_skip;
   // the resident kernel's GRU / LSTM form (resident.hip, RNN): the cell tiled in front
   // of the dense layers, h' carried between requests as granules (an LSTM's c in the
   // owning workgroups' LDS)
   pl.res_rnn = m.has_gru && ((m.gru.cell == 0 && m.gru.lbr == 1) || m.gru.cell == 1) && m.gru.H % 64 == 0 &&
                p.gru.I_pad + m.gru.H <= 512 && (m.gru.H >> 4) <= 256 && pl.latency_shape && o.resident_ms > 0 &&
-               !pl.has_ln && pl.one_round;
+               !pl.has_ln && pl.one_round && !pl.has_skip;
   pl.done_ok = (pl.latency_ok || pl.res_rnn) && p.L[p.nl - 1].N_pad == 16;
   // controller tick: a policy with kHistory x 49 observations and 12 actions
   if (m.in_dim > 0 && m.in_dim % GO2PI_CTL_STEP_DIM == 0 && m.in_dim <= 16 * GO2PI_CTL_STEP_DIM &&
@@ -353,7 +367,8 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   // observation no wider than the hidden layers). The program stays the general body's in
   // every other respect, so the controller tick, the GEMV chain, the single launch and the
   // resident forms run what they run without the bit. Anything else keeps the general body.
-  if ((ln_bits(o) & GO2PI_LN_BATCHED) && pl.has_ln && !m.has_gru && o.waves == 0 && !sw.no_w4 && !sw.no_head_fuse) {
+  if ((ln_bits(o) & GO2PI_LN_BATCHED) && pl.has_ln && !pl.has_skip && !m.has_gru && o.waves == 0 && !sw.no_w4 &&
+      !sw.no_head_fuse) {
     const int tpw = w4_shape_tpw(m), nh = p.nl - 1;
     const bool bare = buf.pre_sub.empty() && buf.pre_div.empty() && buf.pre_mul.empty() && !p.pre_clip &&
                       post_plain(p) && p.lds_stride == 64 * tpw + 4;

@@ -70,6 +70,7 @@ struct HostBuffers {
   std::vector<float> lnpack;     // the LN pipeline's pack (program.hpp w4ln_tpw): biases | Scale | B of the hidden layers
   std::vector<float> gru_w, gru_bzr, gru_bh;
   std::vector<float> pre_sub, pre_div, pre_mul;
+  std::vector<int> skip[GO2PI_MAX_LAYERS];  // each layer's observation column indices (DevProgram::skip_idx)
 };
 
 struct Plan {
@@ -85,6 +86,7 @@ struct Plan {
   bool done_ok = false;        // the final layer is one tile: workgroup 0 signals completion
   bool one_round = false;      // every layer past the first has K_pad <= 512: one sweep round
   bool has_ln = false;         // a LayerNormalization on any layer
+  bool has_skip = false;       // an observation skip input on any layer
   go2pi_cost cost{};
   // whether build() sets up the resident path (the request ring and its kernel)
   bool resident(const go2pi_opts &o) const { return (latency_ok || res_rnn) && done_ok && o.resident_ms > 0; }

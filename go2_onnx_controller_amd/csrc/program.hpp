@@ -98,7 +98,11 @@ struct DevLayer {
   const float *ln_g, *ln_b;  // [N_pad] each, zero padded
   int ln_act;
   float ln_alpha, ln_beta;
-  int pad1;
+  // Observation skip input (onnx_model.hpp Dense::skip): this layer's input is [the previous
+  // layer's N outputs | skip_n columns of the observation after the prologue]; the columns'
+  // indices are DevProgram::skip_idx[l]. On layer 0: a gather of exactly those columns. The
+  // field fills what was padding, so the layer's stride and every other offset stay.
+  int skip_n;
 };
 
 // The recurrent cell in front of the dense head (ONNX GRU or LSTM; the field
@@ -175,20 +179,35 @@ struct DevProgram {
                                // batched kernel adds 1 at its start, an idle resident kernel that sees it
                                // move leaves (it holds CUs the batched kernel needs; resident.hip)
   DevLayer L[GO2PI_MAX_LAYERS];
+  // ---- behind the layers: nothing in front of it moves
+  // layer l's skip_n observation column indices in device memory (null: no skip input)
+  const int *skip_idx[GO2PI_MAX_LAYERS];
 };
 
 // gemv_layer_kernel takes the program by value: a field appended to it moves that kernel's
 // other arguments (and its code). w4ln_tpw fills what was padding in front of w4_bpack, and
 // the LayerNormalization pipeline reads everything else it needs from the hot block and from
-// the layers' own LN fields.
+// the layers' own LN fields. The skip inputs' index tables are appended behind L[] (and
+// DevLayer::skip_n fills that struct's padding): no other field's offset changes, so a kernel
+// that reads the program through a pointer and has no skip code compiles to what it was.
 static_assert(offsetof(DevProgram, w4ln_tpw) == 124 && offsetof(DevProgram, w4_bpack) == 128 &&
-                  offsetof(DevProgram, L) == 312 && sizeof(DevProgram) == 312 + GO2PI_MAX_LAYERS * sizeof(DevLayer),
+                  offsetof(DevProgram, L) == 312 && sizeof(DevLayer) == 80 && offsetof(DevLayer, skip_n) == 76 &&
+                  offsetof(DevProgram, skip_idx) == 312 + GO2PI_MAX_LAYERS * sizeof(DevLayer) &&
+                  sizeof(DevProgram) == 312 + GO2PI_MAX_LAYERS * (sizeof(DevLayer) + sizeof(const int *)),
               "the program's layout is every kernel's ABI");
 
 // a LayerNormalization on any layer (host side: which instantiation a launcher picks)
 inline bool program_has_ln(const DevProgram &p) {
   for (int l = 0; l < p.nl; ++l)
     if (p.L[l].ln) return true;
+  return false;
+}
+
+// an observation skip input on any layer: served by the general batched body and the GEMV
+// chain only (plan.cpp plan_program)
+inline bool program_has_skip(const DevProgram &p) {
+  for (int l = 0; l < p.nl; ++l)
+    if (p.L[l].skip_n) return true;
   return false;
 }
 
@@ -246,8 +265,10 @@ struct DevCtl {  // per call (kernel argument)
 int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves, const float *obs, float *act,
                         float *hidden, int batch, int steps, void *stream);
 size_t fused_lds_bytes(const DevProgram &p, int waves);
-int launch_gemv_layer(const DevProgram &p, int layer, const float *x, int x_stride, float *y, int y_stride,
-                      int batch, void *stream);
+// obs: the call's observation rows [batch][in_dim] (a skip layer's observation columns, and
+// layer 0's input; x is the previous layer's output for layer > 0)
+int launch_gemv_layer(const DevProgram &p, int layer, const float *obs, const float *x, int x_stride, float *y,
+                      int y_stride, int batch, void *stream);
 GemvLds gemv_lds_of(const DevProgram &p, int layer);
 int configure_kernels(const DevProgram &p, int waves);
 // The instantiation launch_policy_fused runs for one tick of fewer than 2^20 rows, as

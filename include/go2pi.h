@@ -89,6 +89,25 @@ void go2pi_default_opts(go2pi_opts *opts);
 
 /* Load an ONNX policy (Gemm/MatMul+Add with Elu/Relu/Tanh/Sigmoid/LeakyRelu, optional GRU)
    and upload it to the device. `opts` may be NULL (defaults).
+   Observation skip inputs (estimator-actor policies: an encoder reads the observation, the
+   actor reads Concat(observation parts, encoder output)): a dense layer may read a Concat on
+   the feature axis (1 or -1) of the previous layer's value (after its activation, post-LN
+   or a held constant Mul / Div) and one or more observation parts, in any order. A part is
+   the observation as layer 0 reads it (after its Sub / Div / Mul / Clip prologue or
+   per-block front-end) or a step-1 Slice of it on the feature axis; Identity may sit
+   anywhere. The Concat must feed a Gemm or MatMul. Layer 0 may itself read a Slice of the
+   observation (a gather: columns it does not read are never multiplied). Several layers,
+   the final one included, may have such an input. Refused with GO2PI_E_MODEL and a message
+   of their own: a Concat of two computed values (two sub-networks joined), a Concat on
+   another axis, a Slice with a step other than 1 or on the batch axis, a part with
+   arithmetic of its own or taken from in front of the prologue, an activation /
+   LayerNormalization / Clip on the concatenation, an Add of two computed values (a residual
+   connection), and any skip input in a policy with a GRU or LSTM cell. Such a policy is
+   served by the general batched kernel and, at batch <= small_batch, by one launch per
+   layer (replayed as a graph); it has no single-launch or resident kernel (resident_ms is
+   accepted and go2pi_resident_kernel reports "none"), ln_small has no effect on it, and
+   go2pi_controller_step* returns GO2PI_E_INVALID for it. go2pi_inspect_model reports each
+   layer's "skip": the observation columns appended to its input, in device order.
    LayerNormalization (opset 17, over the feature axis, epsilon from the attribute, Scale
    and optional B constant, only output 0 used) is accepted on any dense layer but the last,
    once per layer: right after the layer's Gemm / MatMul (+ bias), in front of its
