@@ -191,7 +191,16 @@ __device__ __forceinline__ bool sweep_layer(unsigned long long *gran, int n, uns
 // LNORM: the general instantiation (program.hpp program_small_general): the LayerNormalization
 // pass (opts.ln_small) and a second sweep round for layer inputs of more than 4096
 // granules. Every other program runs the instantiation without either.
-template <bool CTL, bool LNORM = false>
+// SKIP (with LNORM; act() only): the general instantiation of a program with observation skip
+// inputs (DevLayer::skip_n; GO2PI_SKIP_SMALL). A skip layer's columns [prev.N, prev.N + skip_n)
+// of the swept rows are overwritten with prologue(obs[b][idx[j]], idx[j]): the row
+// gemv_layer_kernel stages. obs is pinned host memory here, so a thread's first LAT_SKIPV
+// values (all of them at B * skip_n <= 512 LAT_SKIPV: any skip at batch 1) are loaded in
+// front of the sweep, and only their LDS stores stand behind its barrier. A layer-0 gather
+// stages its columns through the index table.
+constexpr int LAT_SKIPV = 4;
+
+template <bool CTL, bool LNORM = false, bool SKIP = false>
 __device__ __forceinline__ void latency_body(const DevProgram &P, const float *obs, float *act, int B,
                                              unsigned epoch0, unsigned long long *gran, int gstride, unsigned *err,
                                              unsigned *done, const DevCtl ctl) {
@@ -226,6 +235,26 @@ __device__ __forceinline__ void latency_body(const DevProgram &P, const float *o
       wr[s] = c < C ? W[(size_t)c * T * 64] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     const float bv = (wave == LAT_PW && lane < 16) ? L.bias[g * 16 + lane] : 0.f;
+    // SKIP: this layer's skip columns, element e = tid + 512 u of [B][skip_n], in flight
+    // across the sweep (sc: the observation column, for the prologue)
+    const int sn = SKIP ? L.skip_n : 0, sk0 = (SKIP && l > 0) ? P.L[l - 1].N : 0;
+    const int *sidx = SKIP ? P.skip_idx[l] : nullptr;
+    float sv[LAT_SKIPV];
+    int sc[LAT_SKIPV];
+    if constexpr (SKIP) {
+      if (l > 0 && sn) {  // uniform over the workgroup
+#pragma unroll
+        for (int u = 0; u < LAT_SKIPV; ++u) {
+          const int e = tid + u * LAT_WAVES * 64;
+          sv[u] = 0.f, sc[u] = 0;
+          if (e < B * sn) {
+            const int b = e / sn;
+            sc[u] = sidx[e - b * sn];
+            sv[u] = obs[(size_t)b * P.in_dim + sc[u]];
+          }
+        }
+      }
+    }
     if (l == 0) {
       const float *src = obs;
       if constexpr (CTL) {
@@ -234,9 +263,21 @@ __device__ __forceinline__ void latency_body(const DevProgram &P, const float *o
         __syncthreads();
         src = okeep;
       }
-      for (int e = tid; e < B * K_pad; e += LAT_WAVES * 64) {
-        const int b = e / K_pad, k = e - b * K_pad;
-        xs[e] = k < P.in_dim ? prologue(P, src[(size_t)b * P.in_dim + k], k) : 0.f;
+      if (SKIP && sn) {  // a gather: layer 0 reads the columns sidx names, in that order
+        for (int e = tid; e < B * K_pad; e += LAT_WAVES * 64) {
+          const int b = e / K_pad, k = e - b * K_pad;
+          float v = 0.f;
+          if (k < sn) {
+            const int c = sidx[k];
+            v = prologue(P, src[(size_t)b * P.in_dim + c], c);
+          }
+          xs[e] = v;
+        }
+      } else {
+        for (int e = tid; e < B * K_pad; e += LAT_WAVES * 64) {
+          const int b = e / K_pad, k = e - b * K_pad;
+          xs[e] = k < P.in_dim ? prologue(P, src[(size_t)b * P.in_dim + k], k) : 0.f;
+        }
       }
     } else {
       // every wave sweeps its own 512 granules (8 per lane, all in flight), not
@@ -260,11 +301,36 @@ __device__ __forceinline__ void latency_body(const DevProgram &P, const float *o
     // The previous layer's LayerNormalization, as in gemv_layer_kernel: the granules carry
     // its un-normalised output (a pre-LN layer's act is none), every consumer workgroup
     // swept the whole rows, so each normalises its own copy, one row per wave.
+    // SKIP: the skip columns over what the sweep left there (the producer's zero-weight
+    // tiles: act(0)), behind the barrier that ended every wave's sweep stores. ln_rows
+    // touches columns k < prev.N alone, so the two passes share one barrier.
+    bool filled = false;
+    if constexpr (SKIP) {
+      if (l > 0 && sn) {  // uniform over the workgroup
+#pragma unroll
+        for (int u = 0; u < LAT_SKIPV; ++u) {
+          const int e = tid + u * LAT_WAVES * 64;
+          if (e < B * sn) {
+            const int b = e / sn;
+            xs[b * K_pad + sk0 + (e - b * sn)] = prologue(P, sv[u], sc[u]);
+          }
+        }
+        for (int e = tid + LAT_SKIPV * LAT_WAVES * 64; e < B * sn; e += LAT_WAVES * 64) {
+          const int b = e / sn, j = e - b * sn, c = sidx[j];
+          xs[b * K_pad + sk0 + j] = prologue(P, obs[(size_t)b * P.in_dim + c], c);
+        }
+        filled = true;
+      }
+    }
     if constexpr (LNORM) {
       if (l > 0 && P.L[l - 1].ln) {  // uniform over the workgroup
         ln_rows(xs, K_pad, wave, B, LAT_WAVES, ln_of(P.L[l - 1]), lane);
         __syncthreads();
+        filled = false;
       }
+    }
+    if constexpr (SKIP) {
+      if (filled) __syncthreads();
     }
     float p[GO2PI_SMALL_MAXB];
 #pragma unroll
@@ -370,6 +436,14 @@ __global__ __launch_bounds__(LAT_WAVES * 64) void policy_latency_ctl_ln_kernel(c
   latency_body<true, true>(*Pd, nullptr, nullptr, B, epoch0, gran, gstride, err, done, C);
 }
 
+// ... and the general instantiation of a program with observation skip inputs
+__global__ __launch_bounds__(LAT_WAVES * 64) void policy_latency_skip_kernel(const DevProgram *__restrict__ Pd,
+                                                                             const float *obs, float *act, int B,
+                                                                             unsigned epoch0, unsigned long long *gran,
+                                                                             int gstride, unsigned *err, unsigned *done) {
+  latency_body<false, true, true>(*Pd, obs, act, B, epoch0, gran, gstride, err, done, DevCtl{});
+}
+
 int latency_grid(const DevProgram &p) {
   int grid = 1;
   for (int l = 0; l < p.nl; ++l) grid = std::max(grid, p.L[l].N_pad >> 4);
@@ -387,16 +461,19 @@ int launch_latency(const DevProgram &p, const DevProgram *p_dev, const float *ob
   if (batch > GO2PI_SMALL_MAXB) return (int)hipErrorInvalidValue;
   const int grid = latency_grid(p);
   const size_t lds = sizeof(float) * latency_lds_of(p, false).total;
-  hipLaunchKernelGGL(program_small_general(p) ? policy_latency_ln_kernel : policy_latency_kernel, dim3(grid),
-                     dim3(LAT_WAVES * 64), lds, reinterpret_cast<hipStream_t>(stream), p_dev, obs, act, batch, epoch0,
-                     gran, gstride, err, done);
+  hipLaunchKernelGGL(program_has_skip(p)        ? policy_latency_skip_kernel
+                     : program_small_general(p) ? policy_latency_ln_kernel
+                                                : policy_latency_kernel,
+                     dim3(grid), dim3(LAT_WAVES * 64), lds, reinterpret_cast<hipStream_t>(stream), p_dev, obs, act, batch,
+                     epoch0, gran, gstride, err, done);
   return (int)hipGetLastError();
 }
 
 int launch_latency_ctl(const DevProgram &p, const DevProgram *p_dev, const DevCtl &ctl, int batch, unsigned epoch0,
                        unsigned long long *gran, int gstride, unsigned *err, unsigned *done, void *stream) {
   if (batch <= 0) return 0;
-  if (batch > GO2PI_SMALL_MAXB || p.L[p.nl - 1].N_pad != 16) return (int)hipErrorInvalidValue;
+  // (no controller form reads a skip layer's observation columns: the engine refuses the tick)
+  if (batch > GO2PI_SMALL_MAXB || p.L[p.nl - 1].N_pad != 16 || program_has_skip(p)) return (int)hipErrorInvalidValue;
   const int grid = latency_grid(p);
   const size_t lds = sizeof(float) * latency_lds_of(p, true).total;
   hipLaunchKernelGGL(program_small_general(p) ? policy_latency_ctl_ln_kernel : policy_latency_ctl_kernel, dim3(grid),

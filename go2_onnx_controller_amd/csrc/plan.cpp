@@ -200,7 +200,10 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   pl.has_ln = program_has_ln(p);
   // An observation skip input on any layer: the program runs on the general batched body and
   // the GEMV chain alone: no pipeline (w4_eligible), LN pipeline, single launch or resident
-  // form below, and no controller tick (the engine refuses it).
+  // form below, and no controller tick (the engine refuses it). With GO2PI_SKIP_SMALL
+  // (Switches::skip_small) the single launch serves it at batch <= 8 and, of the resident
+  // forms, the multi-workgroup kernel's act() (plan_resident), under the shape conditions of
+  // any dense program.
   pl.has_skip = program_has_skip(p);
   // The 4-wave pipeline (decided below) takes a layer 0 of 3 (mod 4) k-chunks:
   // a 48- or 98-wide observation is padded to 16 columns, not 64 (25 % / 12.5 %
@@ -348,7 +351,9 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
                      !sw.small_chain;  // (the switch: diagnostics, force the GEMV chain)
   // (a LayerNormalization policy: only with opts.ln_small's GO2PI_LN_SMALL bit, ln_bits;
   // latency_body normalises the swept rows as gemv_layer_kernel does)
-  pl.latency_ok = !m.has_gru && pl.latency_shape && (!pl.has_ln || (ln_bits(o) & GO2PI_LN_SMALL)) && !pl.has_skip;
+  // (a policy with observation skip inputs: only with GO2PI_SKIP_SMALL)
+  pl.latency_ok = !m.has_gru && pl.latency_shape && (!pl.has_ln || (ln_bits(o) & GO2PI_LN_SMALL)) &&
+                  (!pl.has_skip || sw.skip_small);
   // the resident kernel's GRU / LSTM form (resident.hip, RNN): the cell tiled in front
   // of the dense layers, h' carried between requests as granules (an LSTM's c in the
   // owning workgroups' LDS)
@@ -435,10 +440,17 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
 // A LayerNormalization policy (opts.ln_small): of these, policy_act1_kernel's act() form
 // only, and no resident controller form (its tick at batch <= 8: policy_latency_ctl_kernel).
 // The controller form serves dense policies whose layer inputs fit one sweep round.
+// A policy with observation skip inputs (GO2PI_SKIP_SMALL): the multi-workgroup kernel's
+// act() and nothing else: the single-workgroup and wide forms keep a layer's input in
+// registers or in layouts with no room for the skip columns, and the tick is refused.
 ResForms plan_resident(const Plan &pl, const Switches &sw, bool resident_ok, bool ring_in_vram) {
   ResForms r;
   if (!resident_ok) return r;
   const DevProgram &p = pl.prog;
+  if (pl.has_skip) {
+    r.act = ResForm::Multi;
+    return r;
+  }
   const bool ln = pl.has_ln;
   const bool better = !p.has_gru && !sw.res_multi;
   const bool act1 = better && !sw.res_r1w && resident_act1_fits(p);

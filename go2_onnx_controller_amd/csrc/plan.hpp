@@ -42,6 +42,9 @@ struct Switches {
   bool res_tiled0;             // RES_TILED0: the multi-workgroup kernel's layer 0 tiled, not local
   int a1_depth, a1_cw;         // A1_DEPTH: policy_act1_kernel's poll sweeps in flight, 1 for the value 1, else 2;
                                // A1_CW: its compute waves, 4 for the value 4, else 8
+  // SKIP_SMALL (opt-in, not a diagnostic): a policy with observation skip inputs at batch <= 8 by the
+  // single launch and the multi-workgroup resident kernel, not the GEMV chain
+  bool skip_small;
 
   static Switches read() {
     auto env = [](const char *name) { return std::getenv(name); };  // (the engine's only look at the environment)
@@ -56,7 +59,7 @@ struct Switches {
                     .gru_general = on("GO2PI_GRU_GENERAL"), .ctl_general = on("GO2PI_CTL_GENERAL"),
                     .res_multi = on("GO2PI_RES_MULTI"), .res_r1w = on("GO2PI_RES_R1W"),
                     .res_tiled0 = on("GO2PI_RES_TILED0"), .a1_depth = num("GO2PI_A1_DEPTH") == 1 ? 1 : 2,
-                    .a1_cw = num("GO2PI_A1_CW") == 4 ? 4 : 8};
+                    .a1_cw = num("GO2PI_A1_CW") == 4 ? 4 : 8, .skip_small = on("GO2PI_SKIP_SMALL")};
   }
 };
 
@@ -86,7 +89,7 @@ struct Plan {
   bool done_ok = false;        // the final layer is one tile: workgroup 0 signals completion
   bool one_round = false;      // every layer past the first has K_pad <= 512: one sweep round
   bool has_ln = false;         // a LayerNormalization on any layer
-  bool has_skip = false;       // an observation skip input on any layer
+  bool has_skip = false;       // an observation skip input on any layer (small-batch kernels: Switches::skip_small)
   go2pi_cost cost{};
   // whether build() sets up the resident path (the request ring and its kernel)
   bool resident(const go2pi_opts &o) const { return (latency_ok || res_rnn) && done_ok && o.resident_ms > 0; }

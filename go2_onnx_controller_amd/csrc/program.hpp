@@ -204,7 +204,8 @@ inline bool program_has_ln(const DevProgram &p) {
 }
 
 // an observation skip input on any layer: served by the general batched body and the GEMV
-// chain only (plan.cpp plan_program)
+// chain, and with GO2PI_SKIP_SMALL by the small-batch kernels' skip instantiations
+// (plan.cpp plan_program)
 inline bool program_has_skip(const DevProgram &p) {
   for (int l = 0; l < p.nl; ++l)
     if (p.L[l].skip_n) return true;
@@ -215,11 +216,14 @@ inline bool program_has_skip(const DevProgram &p) {
 // policy_resident_kernel<.., true>) serve a program with a LayerNormalization, and one
 // whose swept layer inputs can pass the 4096 granules the eight waves take in one round
 // (a layer past the first with K_pad > 512, at batch 5 and up): they sweep a second
-// round. Every other program runs the instantiations without either.
+// round. Every other program runs the instantiations without either. A program with
+// observation skip inputs is a general one too; the launchers give it the general
+// instantiation that also fills the skip columns (policy_latency_skip_kernel,
+// policy_resident_kernel<.., true, true>), so the other general programs run the code they ran.
 inline bool program_small_general(const DevProgram &p) {
   for (int l = 1; l < p.nl; ++l)
     if (p.L[l].K_pad > 512) return true;
-  return program_has_ln(p);
+  return program_has_ln(p) || program_has_skip(p);
 }
 
 // ---------------------------------------------------------------------------

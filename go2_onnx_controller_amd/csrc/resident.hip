@@ -242,6 +242,31 @@ __device__ __forceinline__ void local_layer0(const DevProgram &P, const float4 (
   lds_barrier();
 }
 
+// A skip layer's observation columns (DevLayer::skip_n) into its staged input rows:
+// xs[b][prev.N + j] = prologue(obsv[b][idx[j]], idx[j]), the arithmetic of layer 0's staging
+// loop, so a skip value is the bits layer 0 saw. sc: the caller's prefetched idx[e % skip_n]
+// of elements e = tid + 512 u, u < RES_SKIPV; elements past those read the table here.
+constexpr int RES_SKIPV = 4;
+
+__device__ __forceinline__ void skip_fill(const DevProgram &P, int l, const int (&sc)[RES_SKIPV], const float *obsv,
+                                          float *xs, int B, int tid) {
+  const DevLayer &L = P.L[l];
+  const int sn = L.skip_n, k0 = P.L[l - 1].N, K_pad = L.K_pad, in_dim = P.in_dim;
+#pragma unroll
+  for (int u = 0; u < RES_SKIPV; ++u) {
+    const int e = tid + u * RES_WAVES * 64;
+    if (e < B * sn) {
+      const int b = e / sn;
+      xs[b * K_pad + k0 + (e - b * sn)] = prologue(P, obsv[b * in_dim + sc[u]], sc[u]);
+    }
+  }
+  const int *sidx = P.skip_idx[l];
+  for (int e = tid + RES_SKIPV * RES_WAVES * 64; e < B * sn; e += RES_WAVES * 64) {
+    const int b = e / sn, j = e - b * sn, c = sidx[j];
+    xs[b * K_pad + k0 + j] = prologue(P, obsv[b * in_dim + c], c);
+  }
+}
+
 }  // namespace
 
 // NF > 0: local layer 0 (above) with NF fragments per thread; 0: layer 0 tiled
@@ -274,7 +299,16 @@ __device__ __forceinline__ void local_layer0(const DevProgram &P, const float4 (
 // dense policy only): the LayerNormalization pass on a layer's input (opts.ln_small) and
 // a second sweep round for layer inputs of more than 4096 granules. Every other program
 // runs the instantiations without either.
-template <int NF, bool CTL, int RNN = 0, bool LNORM = false>
+// SKIP (with LNORM): the general instantiation of a program with observation skip inputs
+// (DevLayer::skip_n; GO2PI_SKIP_SMALL). Every workgroup holds the request's raw observation
+// rows in obsv for the whole request, so a skip layer overwrites columns [prev.N, prev.N +
+// skip_n) of its input rows in xs with prologue(obsv[b][idx[j]], idx[j]) (skip_fill): behind
+// the barrier that ends the sweep and the LEAVE check, beside the LN pass (which touches
+// k < prev.N alone) and sharing its barrier; with a local layer 0, layer 1's skip in front of
+// the barrier that ends that path. A thread's first RES_SKIPV indices are loaded in front of
+// the sweep. No granule, tag or wait between workgroups is added. A layer-0 gather runs the
+// tiled layer 0 (launch_resident: multi_nf), staged through the index table.
+template <int NF, bool CTL, int RNN = 0, bool LNORM = false, bool SKIP = false>
 __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const DevProgram *__restrict__ Pd,
                                                                          const u64 *req, u64 *actg, u64 *gran,
                                                                          int gstride, u64 *mirror, unsigned *err,
@@ -283,6 +317,7 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
                                                                          const unsigned *yield) {
   static_assert(!(RNN && (NF > 0 || CTL)), "the GRU form tiles layer 0 and serves act() only");
   static_assert(!(LNORM && (CTL || RNN)), "LayerNormalization: the dense act() form only");
+  static_assert(!SKIP || LNORM, "skip inputs: the general instantiation only");
   constexpr bool LOCAL0 = NF > 0;
   constexpr bool LSTM = RNN == 2;
   constexpr int NG = LSTM ? 4 : 3;  // gate fragments per (chunk, tile)
@@ -584,11 +619,36 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
       const int T = L.N_pad >> 4, C = L.K_pad >> 4, K_pad = L.K_pad;
       if (g >= T) continue;  // this workgroup owns no tile of layer l
       // wr / bv hold layer l (prefetched)
+      // SKIP: the observation columns of this layer's skip elements e = tid + 512 u of
+      // [B][skip_n] (e % skip_n does not depend on B), in flight across the sweep
+      const int sn = SKIP ? L.skip_n : 0;
+      int sc[RES_SKIPV];
+      if constexpr (SKIP) {
+        if (l > 0 && sn) {  // uniform over the workgroup
+          const int *sidx = P.skip_idx[l];
+#pragma unroll
+          for (int u = 0; u < RES_SKIPV; ++u) {
+            const int e = tid + u * RES_WAVES * 64;
+            sc[u] = e < B * sn ? sidx[e % sn] : 0;
+          }
+        }
+      }
       if (l == 0 && RNN) {  // the GRU's h' granules (tag e; row b in buffer 1 - lb[b]), [B][H] = [B][K_pad]
         if (wave < B && sweep<__HIP_MEMORY_SCOPE_AGENT>(hgran + (1u - lb[wave]) * hbuf + (size_t)wave * Hh, Hh, e,
                                                         xs + wave * K_pad, err, lane) != 1 &&
             lane == 0)
           st[0] = 1;
+      } else if (l == 0 && SKIP && sn) {  // a gather: layer 0 reads the columns its index table names
+        const int *sidx = P.skip_idx[0];
+        for (int i = tid; i < B * K_pad; i += RES_WAVES * 64) {
+          const int b = i / K_pad, k = i - b * K_pad;
+          float v = 0.f;
+          if (k < sn) {
+            const int c = sidx[k];
+            v = prologue(P, obsv[b * in_dim + c], c);
+          }
+          xs[i] = v;
+        }
       } else if (l == 0) {
         for (int i = tid; i < B * K_pad; i += RES_WAVES * 64) {
           const int b = i / K_pad, k = i - b * K_pad;
@@ -614,6 +674,10 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
               st[0] = 1;
           }
         }
+      } else if constexpr (SKIP) {
+        // local layer 0 left layer 1's input in xs behind its own last barrier: layer 1's
+        // skip columns go over its padded outputs here, in front of the barrier below
+        if (sn) skip_fill(P, l, sc, obsv, xs, B, tid);
       }
       __syncthreads();
 #ifdef GO2PI_DIAG_RESDBG
@@ -628,11 +692,25 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
       // by local_layer0 (whose last barrier the store of every row precedes), and no wave
       // met a LEAVE tag (st[0], checked first: a half-swept row is never normalised into
       // an answer). Each workgroup normalises its own copy, one row per wave.
+      // SKIP: a swept layer's skip columns over what the sweep left there (the producer's
+      // zero-weight tiles), behind the sweep's barrier and the LEAVE check; one barrier for
+      // this and the LN pass
+      bool filled = false;
+      if constexpr (SKIP) {
+        if (l > 0 && sn && !(LOCAL0 && l == 1)) {  // uniform over the workgroup
+          skip_fill(P, l, sc, obsv, xs, B, tid);
+          filled = true;
+        }
+      }
       if constexpr (LNORM) {
         if (l > 0 && P.L[l - 1].ln) {  // uniform over the workgroup
           ln_rows(xs, K_pad, wave, B, RES_WAVES, ln_of(P.L[l - 1]), lane);
           __syncthreads();
+          filled = false;
         }
+      }
+      if constexpr (SKIP) {
+        if (filled) __syncthreads();
       }
       if (l < 5) RES_STAMP(2 * l + 2);  // layer l's input ready
       float p[GO2PI_SMALL_MAXB];
@@ -1724,9 +1802,10 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
 
 // local layer 0 where each thread's share of it fits NF = 8, 12 or 16 registers' fragments:
 // that NF, else 0 (layer 0 tiled)
+// (a layer-0 gather, DevLayer::skip_n on layer 0: tiled, its staging loop gathers)
 static int multi_nf(const DevProgram &p, bool tiled0) {
   const int nf = local0_geometry(p.L[0].K_pad, p.L[0].N_pad).nf;
-  return (!p.has_gru && p.nl >= 2 && (nf == 8 || nf == 12 || nf == 16) && !tiled0) ? nf : 0;
+  return (!p.has_gru && p.nl >= 2 && (nf == 8 || nf == 12 || nf == 16) && !tiled0 && !p.L[0].skip_n) ? nf : 0;
 }
 
 MultiLds multi_lds_of(const DevProgram &p, bool ctl, bool tiled0) {
@@ -1761,6 +1840,12 @@ int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned
   // (engine.cpp selects neither the controller nor the recurrent form for those)
   const bool gen = program_small_general(p);
   if (gen && (ctl || rnn)) return (int)hipErrorInvalidValue;
+  if (program_has_skip(p)) {  // (a general program: program_small_general)
+    if (local0 && nf == 8) return go(policy_resident_kernel<8, false, 0, true, true>);
+    if (local0 && nf == 12) return go(policy_resident_kernel<12, false, 0, true, true>);
+    if (local0 && nf == 16) return go(policy_resident_kernel<16, false, 0, true, true>);
+    return go(policy_resident_kernel<0, false, 0, true, true>);
+  }
   if (gen) {
     if (local0 && nf == 8) return go(policy_resident_kernel<8, false, 0, true>);
     if (local0 && nf == 12) return go(policy_resident_kernel<12, false, 0, true>);

@@ -104,9 +104,15 @@ void go2pi_default_opts(go2pi_opts *opts);
    LayerNormalization / Clip on the concatenation, an Add of two computed values (a residual
    connection), and any skip input in a policy with a GRU or LSTM cell. Such a policy is
    served by the general batched kernel and, at batch <= small_batch, by one launch per
-   layer (replayed as a graph); it has no single-launch or resident kernel (resident_ms is
-   accepted and go2pi_resident_kernel reports "none"), ln_small has no effect on it, and
-   go2pi_controller_step* returns GO2PI_E_INVALID for it. go2pi_inspect_model reports each
+   layer (replayed as a graph); by default it has no single-launch or resident kernel
+   (resident_ms is accepted and go2pi_resident_kernel reports "none") and ln_small has no
+   effect on it. With GO2PI_SKIP_SMALL set in the environment when the engine is created
+   (to any value; it holds for the engine's life) a dense policy of the single launch's
+   shape is served at batch <= small_batch by policy_latency_kernel and, with
+   resident_ms > 0, by the multi-workgroup policy_resident_kernel (never by a
+   single-workgroup or the wide resident kernel); a policy that also has a
+   LayerNormalization needs ln_small's bit 1 as well. go2pi_controller_step* returns
+   GO2PI_E_INVALID for a policy with a skip input, switch or not. go2pi_inspect_model reports each
    layer's "skip": the observation columns appended to its input, in device order.
    LayerNormalization (opset 17, over the feature axis, epsilon from the attribute, Scale
    and optional B constant, only output 0 used) is accepted on any dense layer but the last,
