@@ -219,6 +219,9 @@ struct go2pi_engine {
   float *d_obs = nullptr;      // host-path staging [max_batch][in]
   float *d_act = nullptr;      // [max_batch][out]
   float *d_tmp[2] = {nullptr, nullptr};  // small-batch activations [SMALL_MAXB][maxw]
+  // a program with residual connections only: the GEMV chain's carried rows [SMALL_MAXB][maxw],
+  // cleared once at build; two, alternated, so a layer never reads the buffer it writes
+  float *d_carry[2] = {nullptr, nullptr};
   int tmp_stride = 0;
   float *h_obs = nullptr, *h_act = nullptr;  // pinned, host-mapped
   float *m_obs = nullptr, *m_act = nullptr;  // device aliases of the above
@@ -623,11 +626,19 @@ struct go2pi_engine {
     } else if (use_chain(batch)) {
       const float *x = obs;
       int xs = prog.in_dim;
+      // residual connections (DevProgram::res): one carried value is live at a time; the
+      // layer that writes the next one writes the other buffer
+      int srcm = 0, cur = 0;
+      for (int l = 0; l < prog.nl; ++l) srcm |= prog.res[l] ? 1 << (prog.res[l] - 1) : 0;
       for (int l = 0; l < prog.nl; ++l) {
         const bool last = l == prog.nl - 1;
         float *y = last ? act : d_tmp[l & 1];
         const int ys = last ? prog.out_dim : tmp_stride;
-        hip_check(go2pi::launch_gemv_layer(prog, l, obs, x, xs, y, ys, (int)batch, s), "gemv_layer launch");
+        const float *cin = prog.res[l] ? d_carry[cur] : nullptr;
+        float *cout = nullptr;
+        if ((srcm >> l) & 1) cout = d_carry[cur ^= 1];
+        hip_check(go2pi::launch_gemv_layer(prog, l, obs, x, xs, y, ys, (int)batch, s, cin, cout, tmp_stride),
+                  "gemv_layer launch");
         x = y;
         xs = ys;
       }
@@ -792,6 +803,11 @@ void build(go2pi_engine &e, const uint8_t *bytes, size_t n, const go2pi_opts *o)
   e.d_act = e.dalloc<float>((size_t)e.opts.max_batch * m.out_dim);
   e.d_tmp[0] = e.dalloc<float>((size_t)GO2PI_SMALL_MAXB * maxw);
   e.d_tmp[1] = e.dalloc<float>((size_t)GO2PI_SMALL_MAXB * maxw);
+  if (plan.has_res)
+    for (float *&c : e.d_carry) {
+      c = e.dalloc<float>((size_t)GO2PI_SMALL_MAXB * maxw);
+      hip_check(hipMemsetAsync(c, 0, sizeof(float) * GO2PI_SMALL_MAXB * maxw, e.stream), "hipMemsetAsync");
+    }
   e.palloc(&e.h_obs, &e.m_obs, sizeof(float) * GO2PI_SMALL_MAXB * m.in_dim);
   e.palloc(&e.h_act, &e.m_act, sizeof(float) * GO2PI_SMALL_MAXB * m.out_dim);
   e.palloc(&e.h_err, &e.m_err, 512);
@@ -1229,6 +1245,10 @@ void check_ctl(const go2pi_engine *e, int64_t batch) {
   if (!e->ctl_hist) throw ApiError("policy I/O is not a Go2 controller's (need 49*k obs, 12 actions)", GO2PI_E_MODEL);
   // (the tick's observation is assembled in LDS and published in place; a skip layer reads
   // the observation rows from memory)
+  // (nor has any controller form a carried tile)
+  if (go2pi::program_has_res(e->prog))
+    throw ApiError("the controller tick does not serve a policy with residual connections "
+                   "(assemble the observation and call go2pi_run)", GO2PI_E_INVALID);
   if (go2pi::program_has_skip(e->prog))
     throw ApiError("the controller tick does not serve a policy with observation skip inputs "
                    "(assemble the observation and call go2pi_run)", GO2PI_E_INVALID);

@@ -223,15 +223,29 @@ __device__ __forceinline__ void load_bias(float4 (&bv)[TPW], const float *__rest
     bv[i] = *reinterpret_cast<const float4 *>(bias + min(t_first + i, T - 1) * 16 + ((lane >> 4) << 2));
 }
 
+// A layer's part in a residual connection (policy_fused_res_kernel; DevProgram::res).
+struct ResTile {
+  float *R = nullptr;  // the carried tile [16][ys], the stride of the activation buffers
+  bool rd = false;     // this layer adds the carried value
+  bool wr = false;     // this layer's stored value is the next carried value
+};
+
 // Epilogue of a hidden layer: bias + activation, one float4 per tile and lane to
 // the LDS activation row (one ds_write_b128 instead of four ds_write_b32); the
 // activated values also go to `keep` (head fusion consumes them from registers).
 // Epilogue of the final layer: bias + activation + post, valid rows/cols to HBM.
-template <int TPW, bool KEEP = false>
+// RES: a consumer layer adds this lane's float4 of the carried tile after the bias and in
+// front of the activation, (acc + bias) + carried; a source layer writes the float4 it stores
+// to Y to the carried tile as well (the raw pre-activation of a pre-LN layer, the activated
+// value otherwise: the LN pass runs afterwards, on Y only). A lane reads and writes only its own
+// elements of the carried tile within a layer (element (rob, 16 t + n0 ..) belongs to tile t's
+// lane, whichever wave runs the tile), and the barrier behind every layer orders the layers, so
+// a layer that is both consumer and source needs no barrier of its own.
+template <int TPW, bool KEEP = false, bool RES = false>
 __device__ __forceinline__ void dense_store(const DevProgram &P, const DevLayer &L, f32x4 (&acc)[TPW],
                                             const float4 (&bv)[TPW], int t_first, int T, int lane, bool last,
                                             float *Y, int ys, float *out, const CtlView ctl, int row0, int B,
-                                            float4 (&keep)[TPW]) {
+                                            float4 (&keep)[TPW], const ResTile rt = {}) {
   const int rob = lane & 15, n0 = (lane >> 4) << 2;
   // fields read once (the final layer's stores would make every element reload them)
   const int LN = L.N;
@@ -244,13 +258,25 @@ __device__ __forceinline__ void dense_store(const DevProgram &P, const DevLayer 
       const int t = t_first + i;
       if (t >= T) continue;
       float4 v;
-      v.x = act_t<ACT>(ap, acc[i][0] + bv[i].x);
-      v.y = act_t<ACT>(ap, acc[i][1] + bv[i].y);
-      v.z = act_t<ACT>(ap, acc[i][2] + bv[i].z);
-      v.w = act_t<ACT>(ap, acc[i][3] + bv[i].w);
+      if constexpr (RES) {
+        float4 s = make_float4(acc[i][0] + bv[i].x, acc[i][1] + bv[i].y, acc[i][2] + bv[i].z, acc[i][3] + bv[i].w);
+        if (rt.rd) {  // uniform over the workgroup
+          const float4 c = *reinterpret_cast<const float4 *>(rt.R + rob * ys + t * 16 + n0);
+          s = make_float4(s.x + c.x, s.y + c.y, s.z + c.z, s.w + c.w);
+        }
+        v = make_float4(act_t<ACT>(ap, s.x), act_t<ACT>(ap, s.y), act_t<ACT>(ap, s.z), act_t<ACT>(ap, s.w));
+      } else {
+        v.x = act_t<ACT>(ap, acc[i][0] + bv[i].x);
+        v.y = act_t<ACT>(ap, acc[i][1] + bv[i].y);
+        v.z = act_t<ACT>(ap, acc[i][2] + bv[i].z);
+        v.w = act_t<ACT>(ap, acc[i][3] + bv[i].w);
+      }
       if (!last) {
         *reinterpret_cast<float4 *>(Y + rob * ys + t * 16 + n0) = v;
         if constexpr (KEEP) keep[i] = v;
+        if constexpr (RES) {
+          if (rt.wr) *reinterpret_cast<float4 *>(rt.R + rob * ys + t * 16 + n0) = v;
+        }
       } else {
         const int row = row0 + rob;
         if (row >= B) continue;
@@ -280,11 +306,11 @@ __device__ __forceinline__ void dense_store(const DevProgram &P, const DevLayer 
 // tiles are exactly its K-chunks of HL, so it multiplies them (read back from
 // LDS by the same wave) against HL's fragments, fetched before its MFMA loop.
 // Partials are summed across waves in a fixed order by head_finish (below).
-template <int TPW, int HT, int RD = 0>
+template <int TPW, int HT, int RD = 0, bool RES = false>
 __device__ __forceinline__ void dense_group(const DevProgram &P, const DevLayer &L, const float *X, float *Y, int xs,
                                             int t_first, int T, int C, int lane, bool last, float *out,
                                             const CtlView ctl, int row0, int B, const DevLayer *HL,
-                                            f32x4 (&hacc)[HT > 0 ? HT : 1]) {
+                                            f32x4 (&hacc)[HT > 0 ? HT : 1], const ResTile rt = {}) {
   constexpr int HN = HT > 0 ? HT : 1;
   f32x4 acc[TPW];
   float4 bv[TPW];
@@ -310,7 +336,7 @@ __device__ __forceinline__ void dense_group(const DevProgram &P, const DevLayer 
     dense_acc<TPW>(X, xs, reinterpret_cast<const float4 *>(L.w), L.N_pad >> 4, t_first, T, 0, C, lane, acc);
   GO2PI_STAMP(P, st, sts + 1);
   float4 yv[TPW];
-  dense_store<TPW, (HT > 0)>(P, L, acc, bv, t_first, T, lane, last, Y, xs, out, ctl, row0, B, yv);
+  dense_store<TPW, (HT > 0), RES>(P, L, acc, bv, t_first, T, lane, last, Y, xs, out, ctl, row0, B, yv, rt);
   GO2PI_STAMP(P, st, sts + 2);
   if constexpr (HT > 0) {
     // the head's B operand for k-chunk t_first + i is exactly the float4 this
@@ -339,10 +365,11 @@ __device__ __forceinline__ void dense_group(const DevProgram &P, const DevLayer 
 
 // Tiles of a wide layer split over the NW waves (full K per wave), optionally
 // with the fused head (HT > 0). Barrier-free.
-template <int NW, int HT>
+template <int NW, int HT, bool RES = false>
 __device__ __forceinline__ void dense_tiles(const DevProgram &P, const DevLayer &L, const float *X, float *Y, int xs,
                                             int wave, int lane, bool last, float *out, const CtlView ctl, int row0,
-                                            int B, const DevLayer *HL, f32x4 (&hacc)[HT > 0 ? HT : 1]) {
+                                            int B, const DevLayer *HL, f32x4 (&hacc)[HT > 0 ? HT : 1],
+                                            const ResTile rt = {}) {
   const int T = L.N_pad >> 4, C = L.K_pad >> 4;
   // largest tile group per pass: bounded so the accumulators fit the VGPR
   // budget of NW waves per CU (512 / (NW/4) registers per lane)
@@ -354,17 +381,17 @@ __device__ __forceinline__ void dense_tiles(const DevProgram &P, const DevLayer 
   int t = wave * tpw;
   const int t_end = min(t + tpw, T);
   for (; t + G <= t_end; t += G) {
-    dense_group<G, HT, RD>(P, L, X, Y, xs, t, T, C, lane, last, out, ctl, row0, B, HL, hacc);
+    dense_group<G, HT, RD, RES>(P, L, X, Y, xs, t, T, C, lane, last, out, ctl, row0, B, HL, hacc, rt);
   }
   const int rem = t_end - t;
   if (G > 4 && rem > 4)
-    dense_group<G, HT, RD>(P, L, X, Y, xs, t, t_end, C, lane, last, out, ctl, row0, B, HL, hacc);
+    dense_group<G, HT, RD, RES>(P, L, X, Y, xs, t, t_end, C, lane, last, out, ctl, row0, B, HL, hacc, rt);
   else if (G > 2 && rem > 2)
-    dense_group<(G > 4 ? 4 : G), HT, RD>(P, L, X, Y, xs, t, t_end, C, lane, last, out, ctl, row0, B, HL, hacc);
+    dense_group<(G > 4 ? 4 : G), HT, RD, RES>(P, L, X, Y, xs, t, t_end, C, lane, last, out, ctl, row0, B, HL, hacc, rt);
   else if (rem == 2)
-    dense_group<2, HT, RD>(P, L, X, Y, xs, t, t_end, C, lane, last, out, ctl, row0, B, HL, hacc);
+    dense_group<2, HT, RD, RES>(P, L, X, Y, xs, t, t_end, C, lane, last, out, ctl, row0, B, HL, hacc, rt);
   else if (rem == 1)
-    dense_group<1, HT, RD>(P, L, X, Y, xs, t, t_end, C, lane, last, out, ctl, row0, B, HL, hacc);
+    dense_group<1, HT, RD, RES>(P, L, X, Y, xs, t, t_end, C, lane, last, out, ctl, row0, B, HL, hacc, rt);
 }
 
 // Layer with the final layer fused in (P.head_fuse = HT tiles): per-wave head
@@ -396,14 +423,14 @@ __device__ __forceinline__ void head_finish(const DevProgram &P, const DevLayer 
 
 // One dense layer for the whole workgroup (NW waves). Contains barriers only in
 // the split-K branch, which every wave of the workgroup takes together.
-template <int NW>
+template <int NW, bool RES = false>
 __device__ __forceinline__ void dense_layer(const DevProgram &P, const DevLayer &L, const float *X, float *Y, int xs,
                                             f32x4 *scratch, int wave, int lane, bool last, float *out,
-                                            const CtlView ctl, int row0, int B) {
+                                            const CtlView ctl, int row0, int B, const ResTile rt = {}) {
   const int T = L.N_pad >> 4, C = L.K_pad >> 4;
   if (T >= NW) {
     f32x4 none[1];
-    dense_tiles<NW, 0>(P, L, X, Y, xs, wave, lane, last, out, ctl, row0, B, nullptr, none);
+    dense_tiles<NW, 0, RES>(P, L, X, Y, xs, wave, lane, last, out, ctl, row0, B, nullptr, none, rt);
   } else {
     // narrow layer (e.g. the 12-action head): split K over waves, reduce in LDS
     const int ks = NW / T;
@@ -422,7 +449,7 @@ __device__ __forceinline__ void dense_layer(const DevProgram &P, const DevLayer 
     if (s == 0) {
       for (int s2 = 1; s2 < ks; ++s2) acc[0] += scratch[(t + s2 * T) * 64 + lane];
       float4 none[1];
-      dense_store<1>(P, L, acc, bv, t, T, lane, last, Y, xs, out, ctl, row0, B, none);
+      dense_store<1, false, RES>(P, L, acc, bv, t, T, lane, last, Y, xs, out, ctl, row0, B, none, rt);
     }
   }
 }
@@ -2018,7 +2045,12 @@ __device__ __forceinline__ void w4_gru_body(const DevProgram &P, const float *ob
 
 // RNN: the recurrent cell this instantiation runs when the program has one (0 GRU,
 // 1 LSTM; one kernel per cell keeps the other cell's registers out of it).
-template <int NW, bool CTL, int W4T = 0, int W4H = 0, int C0M = 0, int RNN = 0, int ACTC = -1, int NHC = 0>
+// RES: the general body with a carried tile (policy_fused_res_kernel): a
+// third activation buffer bufR in the slot a recurrent cell's bufH takes (the two never
+// coexist: the loader refuses a residual connection beside a cell). All of its code stands
+// under `if constexpr (RES)`.
+template <int NW, bool CTL, int W4T = 0, int W4H = 0, int C0M = 0, int RNN = 0, int ACTC = -1, int NHC = 0,
+          bool RES = false>
 __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__restrict__ obs,
                                            float *__restrict__ act, float *__restrict__ hidden, int B, int steps,
                                            const DevCtl ctl) {
@@ -2029,7 +2061,13 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
   float *bufA = lds;
   float *bufB = lds + GO2PI_TILE_ROWS * S;
   float *bufH = lds + 2 * GO2PI_TILE_ROWS * S;  // only with a GRU
-  f32x4 *scratch = reinterpret_cast<f32x4 *>(lds + (2 + P.has_gru) * GO2PI_TILE_ROWS * S);
+  static_assert(!RES || (W4T == 0 && !CTL && RNN == 0), "the carried tile: the general body's act() form only");
+  // the activation buffers in front of the scratch region (fused_lds_bytes): RES, the carried tile
+  auto nbuf = [&] {
+    if constexpr (RES) return 3;
+    else return 2 + P.has_gru;
+  };
+  f32x4 *scratch = reinterpret_cast<f32x4 *>(lds + nbuf() * GO2PI_TILE_ROWS * S);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int row0 = blockIdx.x * GO2PI_TILE_ROWS;
@@ -2067,6 +2105,9 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
   // layer's barrier is scalar arithmetic and waits for no load
   constexpr bool SKIP = W4T == 0 && !CTL && RNN == 0;
   int skipm = 0;
+  // (RES) residual connections, DevProgram::res: consm bit l, layer l adds the carried value;
+  // srcm bit l, layer l's stored value is one. Read here as skipm is, for its reason.
+  [[maybe_unused]] int consm = 0, srcm = 0;
   if constexpr (W4T > 0) {
     // pipeline: no warm-up (holding every descriptor in SGPRs spilled them to VGPR
     // lanes; the fields are read where needed and hit the scalar cache after the
@@ -2076,6 +2117,11 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
     for (int l = 0; l < P.nl; ++l) {
       d ^= P.L[l].K_pad ^ P.L[l].N_pad ^ P.L[l].act ^ (int)(size_t)P.L[l].w;
       if constexpr (SKIP) skipm |= (P.L[l].skip_n != 0) << l;
+      if constexpr (RES) {
+        const int r = P.res[l];  // j + 1, 0: none
+        consm |= (r != 0) << l;
+        srcm |= r ? 1 << (r - 1) : 0;
+      }
     }
     asm volatile("" ::"s"(d));  // consumes the loads; no side effect
   }
@@ -2087,7 +2133,7 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
   // region (one burst of direct-to-LDS loads), then assembled from there
   // per-wave layer hand-off flags (Handoff) behind the scratch region, cleared
   // here; every path passes a workgroup barrier before the first layer
-  float *after_scratch = lds + (2 + P.has_gru) * GO2PI_TILE_ROWS * S + 256 * NW * (P.head_fuse > 1 ? P.head_fuse : 1);
+  float *after_scratch = lds + nbuf() * GO2PI_TILE_ROWS * S + 256 * NW * (P.head_fuse > 1 ? P.head_fuse : 1);
   int *flags = reinterpret_cast<int *>(after_scratch);
   if (tid < NW) flags[tid] = 0;
   int ep = 0;  // hand-offs published so far (identical in every wave)
@@ -2171,6 +2217,16 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
   // observation does not cover, once.
   stage_obs(0);
   GO2PI_STAMP_AT(srow, tid == 0, 41);
+  if constexpr (RES) {
+    // The carried tile, cleared once: a consumer layer's N_pad can pass its source's (a skip
+    // input widens the next layer's K_pad), and a column the source never wrote would be
+    // garbage under a zero weight (NaN * 0 is NaN). Every later value in it is a finite sum of
+    // act(0) constants or a real one. Ordered before the first read by the barrier behind the
+    // observation stage (a layer-0 consumer does not exist).
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 *r4 = reinterpret_cast<float4 *>(bufH);
+    for (int e = tid; e < (GO2PI_TILE_ROWS * S) >> 2; e += NT) r4[e] = z;
+  }
   if (zero_fill) {  // only a GRU whose H is not a multiple of 64 leaves such columns
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     const int tail4 = (S - in_pad0) >> 2;
@@ -2304,7 +2360,8 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
     }
     for (int l = 0; l < P.nl; ++l) {
       const bool last = l == P.nl - 1;
-      if (P.head_fuse && l == P.nl - 2) {
+      // (RES: the planner switches head fusion off for a program with residual connections)
+      if ((RES ? 0 : P.head_fuse) && l == P.nl - 2) {
         if (P.head_fuse == 1)
           dense_layer_head<NW, 1>(P, P.L[l], P.L[l + 1], X, Y, S, scratch, wave, lane, row0, B);
         else dense_layer_head<NW, 2>(P, P.L[l], P.L[l + 1], X, Y, S, scratch, wave, lane, row0, B);
@@ -2315,7 +2372,10 @@ __device__ __forceinline__ void fused_body(const DevProgram &P, const float *__r
         GO2PI_STAMP(P, tid == 0 && step == 0 && l < 8, 7 + l);
         break;  // scratch is next written two barriers later; bufA/bufB are free
       }
-      dense_layer<NW>(P, P.L[l], X, Y, S, scratch, wave, lane, last, ac, cv, row0, B);
+      if constexpr (RES)
+        dense_layer<NW, true>(P, P.L[l], X, Y, S, scratch, wave, lane, last, ac, cv, row0, B,
+                              ResTile{bufH, ((consm >> l) & 1) != 0, ((srcm >> l) & 1) != 0});
+      else dense_layer<NW>(P, P.L[l], X, Y, S, scratch, wave, lane, last, ac, cv, row0, B);
       __syncthreads();  // a workgroup barrier after every layer (dense_acc: flags measured slower)
       if constexpr (W4T == 0) {
         if (P.L[l].ln) {  // uniform over the workgroup: every wave reaches the barrier below
@@ -2381,6 +2441,20 @@ int gen_name(const DevProgram &p, char *buf, size_t cap);  // gen_launch's kerne
 template <int NW>
 int gen_launch_ctl(const DevProgram &p, const DevProgram *p_dev, const DevCtl &ctl, float *hidden, int batch,
                    void *stream);
+
+// The general body with a carried tile: policies with residual connections (fused_body RES).
+// Instantiated for NW = 8 only (kernels_gen_res.hip).
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void policy_fused_res_kernel(const DevProgram *__restrict__ Pd,
+                                                                   const float *__restrict__ obs,
+                                                                   float *__restrict__ act, int B, int steps) {
+  fused_body<NW, false, 0, 0, 0, 0, -1, 0, true>(*Pd, obs, act, nullptr, B, steps, DevCtl{});
+}
+// its host side (kernels_gen_res.hip)
+int res_configure(const DevProgram &p);
+int res_launch(const DevProgram &p, const DevProgram *p_dev, const float *obs, float *act, int batch, int steps,
+               void *stream);
+int res_name(const DevProgram &p, char *buf, size_t cap);
 
 template <int NW, int W4T = 0, int W4H = 0, int C0M = 0, int RNN = 0, int ACTC = -1, int NHC = 0>
 __global__ __launch_bounds__(NW * 64) void policy_fused_kernel(const DevProgram *__restrict__ Pd,

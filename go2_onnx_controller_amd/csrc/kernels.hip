@@ -40,9 +40,17 @@ constexpr int GEMV_WAVES = lds::WAVES;
 // graph: every replay reads the fresh rows), read by a layer with an observation skip input
 // (DevLayer::skip_n): its staged row is [the previous layer's N outputs | obs columns
 // skip_idx[0 .. skip_n) through the prologue], and layer 0's a gather of those columns.
+// cin / cout (residual connections, DevProgram::res; the engine's carry buffers, fixed per
+// engine as the ping-pong buffers are, so a replayed graph reads and writes the same rows):
+// a consumer layer adds cin[b][n] after the bias and in front of the activation,
+// (sum + bias) + carried; a source layer writes the value it stores to y (a pre-LN layer's
+// raw pre-activation: the consumer's staging normalises y, never the carried rows) to
+// cout[b][n] from the thread that writes y. Null: neither. A layer that does both gets two
+// distinct buffers from the engine; each thread touches only its own (b, n) of either.
 __global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram P, int layer, const float *obs,
                                                                      const float *x, int x_stride, float *y,
-                                                                     int y_stride, int B) {
+                                                                     int y_stride, int B, const float *cin,
+                                                                     float *cout, int c_stride) {
   extern __shared__ float4 lds4[];
   const DevLayer &L = P.L[layer];
   const int K_pad = L.K_pad, C = K_pad >> 4, T = L.N_pad >> 4;
@@ -126,11 +134,15 @@ __global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram 
     for (int b = 0; b < B; ++b) {
       float s = 0.f;
       for (int w2 = 0; w2 < GEMV_WAVES; ++w2) s += part[(w2 * GO2PI_SMALL_MAXB + b) * 16 + lane];
-      float v = act_fn(L.act, L.alpha, L.beta, s + bv);
+      float sb = s + bv;
+      // (the carry buffers are cleared when the engine is built: a column no source wrote reads 0)
+      if (cin) sb += cin[(size_t)b * c_stride + n];
+      float v = act_fn(L.act, L.alpha, L.beta, sb);
       if (last) {
         if (n < L.N) y[(size_t)b * y_stride + n] = post_fn(P, v);
       } else {
         y[(size_t)b * y_stride + n] = v;  // padded columns are exact zeros
+        if (cout) cout[(size_t)b * c_stride + n] = v;
       }
     }
   }
@@ -486,7 +498,8 @@ int launch_latency_ctl(const DevProgram &p, const DevProgram *p_dev, const DevCt
 size_t fused_lds_bytes(const DevProgram &p, int waves) {
   // activation buffers + per-wave partial-sum scratch (head fusion: up to 2 tiles)
   // + the layer hand-off flags
-  return sizeof(float) * (size_t)(2 + p.has_gru) * GO2PI_TILE_ROWS * p.lds_stride +
+  // (a program with residual connections: the carried tile, in the recurrent rows' slot)
+  return sizeof(float) * (size_t)(2 + p.has_gru + (program_has_res(p) ? 1 : 0)) * GO2PI_TILE_ROWS * p.lds_stride +
          sizeof(f32x4) * 64 * waves * (p.head_fuse > 1 ? p.head_fuse : 1) + sizeof(float) * GO2PI_FLAG_FLOATS +
          sizeof(float) * p.w4_bias;
 }
@@ -532,7 +545,9 @@ int configure_kernels(const DevProgram &p, int waves) {
     e = (hipError_t)with_w4ln(p, [&](auto t) { return w4ln_configure<decltype(t)::value>(p); });
     if (e != hipSuccess) return (int)e;
   }
-  if (waves == 4 && p.w4_tpw)
+  if (program_has_res(p))  // (kernels_gen_res.hip; the planner gives it 8 waves)
+    e = (hipError_t)res_configure(p);
+  else if (waves == 4 && p.w4_tpw)
     e = (hipError_t)with_w4(p, [&](auto t) { return w4_configure<decltype(t)::value>(p); });
   else
     e = (hipError_t)with_waves(waves, [&](auto w) { return gen_configure<decltype(w)::value>(p); });
@@ -547,6 +562,7 @@ int configure_kernels(const DevProgram &p, int waves) {
 int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves, const float *obs, float *act,
                         float *hidden, int batch, int steps, void *stream) {
   if (batch <= 0 || steps <= 0) return 0;
+  if (program_has_res(p)) return waves == 8 ? res_launch(p, p_dev, obs, act, batch, steps, stream) : (int)hipErrorInvalidValue;
   if (p.w4ln_tpw)
     return with_w4ln(p, [&](auto t) {
       return w4ln_launch<decltype(t)::value>(p, p_dev, obs, act, batch, steps, stream);
@@ -561,6 +577,7 @@ int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves,
 }
 
 int batched_kernel_name(const DevProgram &p, int waves, char *buf, size_t cap) {
+  if (program_has_res(p)) return res_name(p, buf, cap);
   if (p.w4ln_tpw) return with_w4ln(p, [&](auto t) { return w4ln_name<decltype(t)::value>(p, buf, cap); });
   if (waves == 4 && p.w4_tpw) return with_w4(p, [&](auto t) { return w4_name<decltype(t)::value>(p, buf, cap); });
   return with_waves(waves, [&](auto w) { return gen_name<decltype(w)::value>(p, buf, cap); });
@@ -582,12 +599,15 @@ int launch_policy_fused_ctl(const DevProgram &p, const DevProgram *p_dev, int wa
 }
 
 int launch_gemv_layer(const DevProgram &p, int layer, const float *obs, const float *x, int x_stride, float *y,
-                      int y_stride, int batch, void *stream) {
+                      int y_stride, int batch, void *stream, const float *cin, float *cout, int c_stride) {
   if (batch <= 0) return 0;
   if (batch > GO2PI_SMALL_MAXB) return (int)hipErrorInvalidValue;
+  // a residual layer without its carried rows, or one buffer for both directions
+  if ((p.res[layer] != 0) != (cin != nullptr) || (cin && cin == cout)) return (int)hipErrorInvalidValue;
   const dim3 grid(p.L[layer].N_pad >> 4);
   hipLaunchKernelGGL(gemv_layer_kernel, grid, dim3(GEMV_WAVES * 64), sizeof(float) * gemv_lds_of(p, layer).total,
-                     reinterpret_cast<hipStream_t>(stream), p, layer, obs, x, x_stride, y, y_stride, batch);
+                     reinterpret_cast<hipStream_t>(stream), p, layer, obs, x, x_stride, y, y_stride, batch, cin, cout,
+                     c_stride);
   return (int)hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <unordered_map>
@@ -393,6 +394,18 @@ struct GraphView {
     if (nd.op == "Concat") return true;
     return (nd.op == "Slice" || nd.op == "Identity") && !nd.out.empty() && to_concat(nd.out[0], depth + 1);
   }
+  // v, through Slice / Identity alone, is an operand of an Add of two computed values (the
+  // observation as the added operand of a residual connection: refused)
+  bool to_res_add(const std::string &v, int depth = 0) const {
+    auto it = consumers.find(v);
+    if (it == consumers.end() || depth > 16) return false;
+    for (size_t c : it->second) {
+      const Node &nd = nodes[c];
+      if (nd.op == "Add" && nd.in.size() >= 2 && !inits.count(nd.in[0]) && !inits.count(nd.in[1])) return true;
+      if ((nd.op == "Slice" || nd.op == "Identity") && !nd.out.empty() && to_res_add(nd.out[0], depth + 1)) return true;
+    }
+    return false;
+  }
   // A Slice of the observation (its output v) that is no front-end block: its chain
   // feeds a Gemm / MatMul (layer 0 reads a slice) or a Concat that also
   // takes a value not computed from the observation alone (a skip Concat). A front-end
@@ -443,6 +456,8 @@ void front_end(Model &m, const std::vector<Node> &nodes, const std::unordered_ma
   size_t n_slice = 0, n_skip = 0;
   for (size_t k : ci->second)
     if (nodes[k].op == "Slice" && !nodes[k].out.empty()) {
+      if (gv.to_res_add(nodes[k].out[0]))
+        fail("the observation (or a Slice of it) as the added operand of a residual connection is unsupported");
       ++n_slice;
       n_skip += gv.skip_slice(nodes[k].out[0]) ? 1 : 0;
     }
@@ -728,6 +743,49 @@ Model parse_onnx(const uint8_t *data, size_t n) {
     }
     return c;
   };
+  // Residual connections (onnx_model.hpp Dense::res). tap: the one carried value that is live,
+  // the tensor (named in front of any Identity) that holds layer `layer`'s carried value and
+  // that a later Add behind a Gemm / MatMul closes. Only one is live at a time.
+  struct {
+    bool on = false;
+    std::string name;
+    int layer = -1;
+  } tap;
+  auto real_add = [&](size_t k) {  // an Add of two computed values
+    const Node &a = nodes[k];
+    return a.op == "Add" && a.in.size() >= 2 && !inits.count(a.in[0]) && !inits.count(a.in[1]);
+  };
+  // node k is the closing Add of a residual connection, or an Identity on the way to one
+  std::function<bool(size_t, int)> add_ward = [&](size_t k, int depth) -> bool {
+    if (real_add(k)) return true;
+    const Node &a = nodes[k];
+    if (a.op != "Identity" || a.out.empty() || depth > 16) return false;
+    auto ci = consumers.find(a.out[0]);
+    if (ci == consumers.end() || ci->second.empty()) return false;
+    for (size_t c : ci->second)
+      if (!add_ward(c, depth + 1)) return false;
+    return true;
+  };
+  // ... the same from the observation, through Slices too (refused where the Add is reached)
+  std::function<bool(size_t, int)> obs_to_add = [&](size_t k, int depth) -> bool {
+    if (real_add(k)) return true;
+    const Node &a = nodes[k];
+    if ((a.op != "Identity" && a.op != "Slice") || a.out.empty() || depth > 16) return false;
+    auto ci = consumers.find(a.out[0]);
+    if (ci == consumers.end()) return false;
+    for (size_t c : ci->second)
+      if (obs_to_add(c, depth + 1)) return true;
+    return false;
+  };
+  // the first operator behind node k that is no Identity
+  auto real_op = [&](size_t k) -> std::string {
+    for (int hop = 0; hop < 64 && nodes[k].op == "Identity" && !nodes[k].out.empty(); ++hop) {
+      auto ci = consumers.find(nodes[k].out[0]);
+      if (ci == consumers.end() || ci->second.size() != 1) break;
+      k = ci->second[0];
+    }
+    return nodes[k].op;
+  };
   bool last_has_act = true;  // true => next Add cannot fold into a bias
   bool pending_bias_ok = false;
   // elementwise ops after the last layer's activation: a Mul by a constant is held
@@ -753,6 +811,11 @@ Model parse_onnx(const uint8_t *data, size_t n) {
   // except a held column scale, folded into its weights here
   auto begin_layer = [&](Dense &d, const std::string &op) {
     if (post_clip) fail(op + ": a Clip after an activation is only supported at the end of the graph");
+    // (I + W) z: no exported architecture writes it, and the sum would be a layer output
+    // with no epilogue of its own
+    if (!m.layers.empty() && m.layers.back().res >= 0 && !last_has_act && !m.layers.back().ln)
+      fail(op + ": the sum of a residual connection feeds it with neither an activation nor a LayerNormalization "
+           "on the sum (Gemm -> Add -> Gemm), which is unsupported");
     int nrun = d.K;  // the columns that read the previous layer's outputs
     if (pend.on) {
       // the skip Concat in front: W's columns into device order (running value first, then
@@ -795,10 +858,54 @@ Model parse_onnx(const uint8_t *data, size_t n) {
           ++n_unused;
         }
     // the observation with skip branches: the main chain is the consumer that does not
-    // lead, through Slice / Identity alone, to a Concat
-    if (n_unused > 1)
+    // lead, through Slice / Identity alone, to a Concat (nor to a residual Add, which is
+    // refused where the chain reaches it)
+    const bool in_front = m.layers.empty() && !m.has_gru;
+    bool tapped = false;
+    if (n_unused > 1 && !in_front)
+      for (size_t k : it->second) tapped |= !used[k] && add_ward(k, 0);
+    if (tapped) {
+      // A residual connection's tap: the value has two consumers, the main chain and the
+      // closing Add (through Identity). Follow the main chain and remember the tensor.
+      size_t n_add = 0, n_main = 0, main = SIZE_MAX;
+      for (size_t k : it->second) {
+        if (used[k]) continue;
+        if (add_ward(k, 0)) ++n_add;
+        else if (n_main++ == 0) main = k;
+      }
+      if (m.has_gru) fail("a residual connection in a policy with a GRU or LSTM cell is unsupported");
+      if (n_add > 1) fail("the tap '" + cur + "' of a residual connection is consumed by more than one Add");
+      if (n_main != 1 || it->second.size() > 2)
+        fail("a value with more than two consumers ('" + cur + "') cannot be the tap of a residual connection");
+      if (tap.on)
+        fail("nested or overlapping residual connections are unsupported: '" + cur + "' is tapped while the one from "
+             "layer " + std::to_string(tap.layer) + " is open");
+      const Dense &d = m.layers.back();
+      const std::string mop = real_op(main);
+      const bool mact = act_of(mop) >= 0 || mop == "Clip";
+      if (d.ln)
+        fail("a residual connection tapped from a LayerNormalization's output (or behind it) is unsupported: the "
+             "carried value of a layer with a LayerNormalization is that LayerNormalization's input");
+      if (post_clip || !col_scale.empty() || (last_has_act && (mop == "Mul" || mop == "Div")))
+        fail("a residual connection from a layer with a constant Mul / Div (or Clip) behind its activation is "
+             "unsupported");
+      if (!last_has_act && mact)
+        fail("a residual connection tapped between a Gemm / MatMul and its activation is unsupported (tap the "
+             "activation's output, or the input of a LayerNormalization)");
+      if (mop != "LayerNormalization" && mop != "Gemm" && mop != "MatMul" && mop != "Concat")
+        fail("the tap of a residual connection must feed a LayerNormalization, the next Gemm / MatMul or a skip "
+             "Concat, not '" + mop + "'");
+      tap.on = true;
+      tap.name = canon(cur);
+      tap.layer = (int)m.layers.size() - 1;
+      idx = main;
+    } else if (n_unused > 1) {
       for (size_t k : it->second)
         if (!used[k] && !gv.node_to_concat(k)) { idx = k; break; }
+      if (in_front)
+        for (size_t k : it->second)
+          if (!used[k] && !gv.node_to_concat(k) && !obs_to_add(k, 0)) { idx = k; break; }
+    }
     if (idx == SIZE_MAX) fail("dangling value '" + cur + "' does not reach output '" + final_out + "'");
     used[idx] = true;
     const Node &nd = nodes[idx];
@@ -892,6 +999,26 @@ Model parse_onnx(const uint8_t *data, size_t n) {
       d.ln_eps = nd.fattr("epsilon", 1e-5f);
       d.ln = last_has_act ? 2 : 1;
       pending_bias_ok = false;
+    } else if (real_add(idx)) {
+      // a residual connection's closing Add: lowered directly behind a layer's Gemm / MatMul
+      // (+ bias), against the live tap (Dense::res)
+      if (gv.obs_derived(other_input()))
+        fail("the observation (or a Slice of it) as the added operand of a residual connection is unsupported (node '" +
+             nd.name + "')");
+      if (!tap.on || canon(other_input()) != tap.name)
+        fail("Add of two computed values (a residual connection) is unsupported (node '" + nd.name + "')");
+      if (m.has_gru) fail("a residual connection in a policy with a GRU or LSTM cell is unsupported");
+      Dense &d = m.layers.back();
+      const int l = (int)m.layers.size() - 1;
+      if (last_has_act || d.ln || l <= tap.layer || d.res >= 0)
+        fail("a residual connection added behind a layer's activation or LayerNormalization (x + act(Wx), x + LN(..)) "
+             "is unsupported: the Add is lowered only directly behind the Gemm / MatMul (node '" + nd.name + "')");
+      if (m.layers[tap.layer].N != d.N)
+        fail("a residual connection adds the " + std::to_string(m.layers[tap.layer].N) + " features of layer " +
+             std::to_string(tap.layer) + " to the " + std::to_string(d.N) + " of layer " + std::to_string(l));
+      d.res = tap.layer;
+      tap.on = false;
+      pending_bias_ok = false;
     } else if (!m.layers.empty() && m.layers.back().ln == 1 && !last_has_act &&
                (nd.op == "Add" || nd.op == "Mul" || nd.op == "Div" || nd.op == "Sub")) {
       fail(nd.op + " between a LayerNormalization and its activation is unsupported");
@@ -970,6 +1097,8 @@ Model parse_onnx(const uint8_t *data, size_t n) {
       if (!last_has_act) {
         // straight after Gemm (+ bias): scale the layer's rows and bias
         Dense &d = m.layers.back();
+        if (d.res >= 0)
+          fail("a constant " + nd.op + " between the Add of a residual connection and the activation is unsupported");
         const std::vector<float> sc = const_vec(C, d.N, nd.op);
         for (int i = 0; i < d.N; ++i) {
           const float f = div ? 1.f / sc[i] : sc[i];
@@ -1087,6 +1216,8 @@ Model parse_onnx(const uint8_t *data, size_t n) {
   if (pend.on) fail("a skip Concat must feed a Gemm or MatMul: it is the graph's output");
   if (m.layers.empty()) fail("policy has no linear layer");
   if (m.layers.back().ln) fail("LayerNormalization on the output layer is unsupported");
+  if (m.layers.back().res >= 0) fail("a residual connection on the output layer is unsupported");
+  if (tap.on) fail("the tap of a residual connection from layer " + std::to_string(tap.layer) + " is never added");
   if (rnn_node != SIZE_MAX) {
     // The recurrent state I/O listed as (h, c) after the observation / action, whatever
     // the graph's order: traced by name to the cell's initial_h / initial_c (inputs 5,
@@ -1239,7 +1370,7 @@ std::string inspect_json(const Model &m) {
          ",\"ln\":" + std::to_string(d.ln) + ",\"ln_eps\":" + json_num(d.ln_eps) +
          ",\"ln_g_sum\":" + json_num(sum_of(d.ln_g)) + ",\"ln_b_sum\":" + json_num(sum_of(d.ln_b)) + ",\"skip\":[";
     for (size_t i = 0; i < d.skip.size(); ++i) j += (i ? "," : "") + std::to_string(d.skip[i]);
-    j += "]}";
+    j += "],\"res\":" + std::to_string(d.res) + "}";
   }
   j += "],\"gru\":";
   if (m.has_gru)

@@ -1,7 +1,8 @@
 // ONNX policy loader: a minimal protobuf reader plus a pattern matcher that
 // lowers an exported policy graph to the engine's program (dense layers with a
 // fused activation, an optional LayerNormalization and an optional observation skip input
-// (Concat of the previous layer's value and Slices of the observation), optional leading GRU,
+// (Concat of the previous layer's value and Slices of the observation) and an optional residual
+// connection (Add of the layer's Gemm output and an earlier layer's carried value), optional leading GRU,
 // optional affine prologue and clip epilogue). Replaces what the reference gets from onnxruntime's session
 // creation (onnx_inference/src/cpp/onnx_actor.cpp:16, :23-28).
 #pragma once
@@ -40,6 +41,13 @@ struct Dense {
   // W's columns are in that (device) order. On layer 0, which has no previous layer, a
   // non-empty skip is a gather: the layer reads exactly these columns of x0. Empty: none.
   std::vector<int> skip;
+  // Residual connection: the index j < l of the layer whose carried value c_j is added to this
+  // layer's Gemm / MatMul (+ bias) output, in front of its LayerNormalization and activation:
+  //   s_l = (Gemm_l(input_l) + b_l) + c_j,   o_l = [post-LN](act_l([pre-LN](s_l)))
+  // c_j is the input of layer j's LayerNormalization where it has one (s_j for a pre-LN
+  // layer, act_j(s_j) for a post-LN one), else its output o_j: the value layer j's dense
+  // store writes before any LN pass touches it. N_j == N_l. -1: none.
+  int res = -1;
 };
 
 // ONNX GRU (opset 14), forward, layout 0, one layer; gates ordered z, r, h.

@@ -90,8 +90,9 @@ int w4_shape_tpw(const Model &m) {
 bool w4_eligible(const Model &m, const go2pi_opts &o, const Switches &sw, bool ln) {
   const int nl = (int)m.layers.size();
   // an observation skip input: the general body and the GEMV chain only
+  // ... and a residual connection: the general body's residual instantiation and the chain
   for (const auto &d : m.layers)
-    if (!d.skip.empty()) return false;
+    if (!d.skip.empty() || d.res >= 0) return false;
   if (!(o.waves == 0 || o.waves == 4) || nl < 2) return false;
   if (m.has_gru && m.gru.H % 64) return false;
   if (m.has_gru && m.gru.cell == 0 && m.gru.lbr == 0) return false;  // the two-pass cell: generic body only
@@ -177,6 +178,8 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
     L.N = d.N;
     L.skip_n = (int)d.skip.size();
     buf.skip[l] = d.skip;
+    p.res[l] = d.res + 1;
+    if (d.res >= 0) flops += d.N;  // the carried value's add
     L.act = d.act;
     L.alpha = d.alpha;
     L.beta = d.beta;
@@ -205,6 +208,15 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   // forms, the multi-workgroup kernel's act() (plan_resident), under the shape conditions of
   // any dense program.
   pl.has_skip = program_has_skip(p);
+  // A residual connection on any layer: policy_fused_res_kernel<8> (the general body with a
+  // carried tile, kernels_gen_res.hip) for batched launches and the GEMV chain at batch <=
+  // small_batch; nothing else. Only the 8-wave instantiation is built (a general-body unit
+  // takes minutes to compile), so an explicit waves = 4 or 16 is refused, and the
+  // GO2PI_LN_BATCHED, ln_small and GO2PI_SKIP_SMALL bits have no effect on such a program.
+  pl.has_res = program_has_res(p);
+  if (pl.has_res && (o.waves == 4 || o.waves == 16))
+    throw ApiError("a policy with residual connections runs on the 8-wave batched kernel only: waves = " +
+                   std::to_string(o.waves) + " is not available for it (use 0 or 8)", GO2PI_E_INVALID);
   // The 4-wave pipeline (decided below) takes a layer 0 of 3 (mod 4) k-chunks:
   // a 48- or 98-wide observation is padded to 16 columns, not 64 (25 % / 12.5 %
   // fewer layer-0 MFMAs and fragment bytes). Other kernels take any chunk count.
@@ -273,7 +285,10 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
     const int t_last = p.L[p.nl - 1].N_pad / 16, t_prev = p.L[p.nl - 2].N_pad / 16;
     // (not behind a LayerNormalization: dense_layer_head feeds the head from un-normalised registers)
     // (nor a head with a skip input: its observation columns are not in those registers)
-    if (t_last <= 2 && t_prev >= pl.waves && !p.L[p.nl - 2].ln && !p.L[p.nl - 1].skip_n) p.head_fuse = t_last;
+    // (nor a program with residual connections: switched off for it, so that the layer in front
+    // of the head, which may carry a sum, runs the one dense store every other layer runs)
+    if (t_last <= 2 && t_prev >= pl.waves && !p.L[p.nl - 2].ln && !p.L[p.nl - 1].skip_n && !pl.has_res)
+      p.head_fuse = t_last;
   }
   // 4-wave uniform-MLP pipeline (kernels.hip, w4_step): a fused head, and
   // every hidden layer exactly one group of 2, 4 or 8 tiles per wave. It is the
@@ -336,7 +351,10 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   const size_t lds = fused_lds_bytes(p, pl.waves);
   if (lds > 160 * 1024)
     throw ApiError("layer width " + std::to_string(maxw) + " needs " + std::to_string(lds) +
-                   " B of LDS per tile (> 160 KiB)", GO2PI_E_MODEL);
+                   " B of LDS per tile (> 160 KiB)" +
+                   (pl.has_res ? ": a policy with residual connections holds a third activation buffer, the carried tile"
+                               : ""),
+                   GO2PI_E_MODEL);
 
   // a layer past the first with more than 512 input columns: at batch 5 and up its input
   // rows pass the 4096 granules one sweep round takes. The single launch and the
@@ -353,13 +371,13 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   // latency_body normalises the swept rows as gemv_layer_kernel does)
   // (a policy with observation skip inputs: only with GO2PI_SKIP_SMALL)
   pl.latency_ok = !m.has_gru && pl.latency_shape && (!pl.has_ln || (ln_bits(o) & GO2PI_LN_SMALL)) &&
-                  (!pl.has_skip || sw.skip_small);
+                  (!pl.has_skip || sw.skip_small) && !pl.has_res;
   // the resident kernel's GRU / LSTM form (resident.hip, RNN): the cell tiled in front
   // of the dense layers, h' carried between requests as granules (an LSTM's c in the
   // owning workgroups' LDS)
   pl.res_rnn = m.has_gru && ((m.gru.cell == 0 && m.gru.lbr == 1) || m.gru.cell == 1) && m.gru.H % 64 == 0 &&
                p.gru.I_pad + m.gru.H <= 512 && (m.gru.H >> 4) <= 256 && pl.latency_shape && o.resident_ms > 0 &&
-               !pl.has_ln && pl.one_round && !pl.has_skip;
+               !pl.has_ln && pl.one_round && !pl.has_skip && !pl.has_res;
   pl.done_ok = (pl.latency_ok || pl.res_rnn) && p.L[p.nl - 1].N_pad == 16;
   // controller tick: a policy with kHistory x 49 observations and 12 actions
   if (m.in_dim > 0 && m.in_dim % GO2PI_CTL_STEP_DIM == 0 && m.in_dim <= 16 * GO2PI_CTL_STEP_DIM &&
@@ -372,8 +390,8 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   // observation no wider than the hidden layers). The program stays the general body's in
   // every other respect, so the controller tick, the GEMV chain, the single launch and the
   // resident forms run what they run without the bit. Anything else keeps the general body.
-  if ((ln_bits(o) & GO2PI_LN_BATCHED) && pl.has_ln && !pl.has_skip && !m.has_gru && o.waves == 0 && !sw.no_w4 &&
-      !sw.no_head_fuse) {
+  if ((ln_bits(o) & GO2PI_LN_BATCHED) && pl.has_ln && !pl.has_skip && !pl.has_res && !m.has_gru && o.waves == 0 &&
+      !sw.no_w4 && !sw.no_head_fuse) {
     const int tpw = w4_shape_tpw(m), nh = p.nl - 1;
     const bool bare = buf.pre_sub.empty() && buf.pre_div.empty() && buf.pre_mul.empty() && !p.pre_clip &&
                       post_plain(p) && p.lds_stride == 64 * tpw + 4;

@@ -90,6 +90,7 @@ struct Plan {
   bool one_round = false;      // every layer past the first has K_pad <= 512: one sweep round
   bool has_ln = false;         // a LayerNormalization on any layer
   bool has_skip = false;       // an observation skip input on any layer (small-batch kernels: Switches::skip_small)
+  bool has_res = false;        // a residual connection on any layer (policy_fused_res_kernel<8> and the GEMV chain)
   go2pi_cost cost{};
   // whether build() sets up the resident path (the request ring and its kernel)
   bool resident(const go2pi_opts &o) const { return (latency_ok || res_rnn) && done_ok && o.resident_ms > 0; }

@@ -182,6 +182,10 @@ struct DevProgram {
   // ---- behind the layers: nothing in front of it moves
   // layer l's skip_n observation column indices in device memory (null: no skip input)
   const int *skip_idx[GO2PI_MAX_LAYERS];
+  // Residual connections (onnx_model.hpp Dense::res): res[l] = j + 1 where layer j's carried
+  // value is added to layer l's Gemm (+ bias) output in front of its activation / LN, 0: none
+  // (so a zeroed program has none). Served by policy_fused_res_kernel and the GEMV chain.
+  int res[GO2PI_MAX_LAYERS];
 };
 
 // gemv_layer_kernel takes the program by value: a field appended to it moves that kernel's
@@ -190,10 +194,13 @@ struct DevProgram {
 // the layers' own LN fields. The skip inputs' index tables are appended behind L[] (and
 // DevLayer::skip_n fills that struct's padding): no other field's offset changes, so a kernel
 // that reads the program through a pointer and has no skip code compiles to what it was.
+// The residual table res[] stands behind skip_idx[] for the same reason.
 static_assert(offsetof(DevProgram, w4ln_tpw) == 124 && offsetof(DevProgram, w4_bpack) == 128 &&
                   offsetof(DevProgram, L) == 312 && sizeof(DevLayer) == 80 && offsetof(DevLayer, skip_n) == 76 &&
                   offsetof(DevProgram, skip_idx) == 312 + GO2PI_MAX_LAYERS * sizeof(DevLayer) &&
-                  sizeof(DevProgram) == 312 + GO2PI_MAX_LAYERS * (sizeof(DevLayer) + sizeof(const int *)),
+                  offsetof(DevProgram, res) == 312 + GO2PI_MAX_LAYERS * (sizeof(DevLayer) + sizeof(const int *)) &&
+                  sizeof(DevProgram) ==
+                      (312 + GO2PI_MAX_LAYERS * (sizeof(DevLayer) + sizeof(const int *) + sizeof(int)) + 7) / 8 * 8,
               "the program's layout is every kernel's ABI");
 
 // a LayerNormalization on any layer (host side: which instantiation a launcher picks)
@@ -209,6 +216,14 @@ inline bool program_has_ln(const DevProgram &p) {
 inline bool program_has_skip(const DevProgram &p) {
   for (int l = 0; l < p.nl; ++l)
     if (p.L[l].skip_n) return true;
+  return false;
+}
+
+// a residual connection on any layer: served by the general batched body's residual
+// instantiation (policy_fused_res_kernel<8>) and the GEMV chain only (plan.cpp plan_program)
+inline bool program_has_res(const DevProgram &p) {
+  for (int l = 0; l < p.nl; ++l)
+    if (p.res[l]) return true;
   return false;
 }
 
@@ -271,8 +286,11 @@ int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves,
 size_t fused_lds_bytes(const DevProgram &p, int waves);
 // obs: the call's observation rows [batch][in_dim] (a skip layer's observation columns, and
 // layer 0's input; x is the previous layer's output for layer > 0)
+// cin / cout: the carried value's rows [batch][c_stride] a residual consumer layer adds / a
+// source layer writes beside y (null: neither). Distinct buffers where a layer does both.
 int launch_gemv_layer(const DevProgram &p, int layer, const float *obs, const float *x, int x_stride, float *y,
-                      int y_stride, int batch, void *stream);
+                      int y_stride, int batch, void *stream, const float *cin = nullptr, float *cout = nullptr,
+                      int c_stride = 0);
 GemvLds gemv_lds_of(const DevProgram &p, int layer);
 int configure_kernels(const DevProgram &p, int waves);
 // The instantiation launch_policy_fused runs for one tick of fewer than 2^20 rows, as

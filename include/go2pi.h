@@ -101,8 +101,8 @@ void go2pi_default_opts(go2pi_opts *opts);
    of their own: a Concat of two computed values (two sub-networks joined), a Concat on
    another axis, a Slice with a step other than 1 or on the batch axis, a part with
    arithmetic of its own or taken from in front of the prologue, an activation /
-   LayerNormalization / Clip on the concatenation, an Add of two computed values (a residual
-   connection), and any skip input in a policy with a GRU or LSTM cell. Such a policy is
+   LayerNormalization / Clip on the concatenation, an Add of two computed values that is no
+   residual connection of the form below, and any skip input in a policy with a GRU or LSTM cell. Such a policy is
    served by the general batched kernel and, at batch <= small_batch, by one launch per
    layer (replayed as a graph); by default it has no single-launch or resident kernel
    (resident_ms is accepted and go2pi_resident_kernel reports "none") and ln_small has no
@@ -114,6 +114,23 @@ void go2pi_default_opts(go2pi_opts *opts);
    LayerNormalization needs ln_small's bit 1 as well. go2pi_controller_step* returns
    GO2PI_E_INVALID for a policy with a skip input, switch or not. go2pi_inspect_model reports each
    layer's "skip": the observation columns appended to its input, in device order.
+   Residual connections (SimBa blocks, ResNet-v1 MLPs): an Add, in either operand order, of
+   a layer's Gemm / MatMul (+ bias) output, in front of its LayerNormalization and activation,
+   and an earlier layer's carried value (possibly through Identity): the input of that
+   layer's LayerNormalization where it has one, else its output; equal widths; one carried
+   value live at a time (a chain of blocks, no nesting or overlap). Refused with
+   GO2PI_E_MODEL and a message that names the "residual connection": a carried value with
+   more than two consumers or more than one Add, the observation as the added operand, an
+   Add on the output layer, behind an activation or a LayerNormalization, or whose sum
+   feeds the next Gemm with neither on it, a tap between a Gemm and its activation or from a
+   LayerNormalization's output, a held constant Mul / Div on the source, and any residual
+   connection beside a GRU or LSTM cell. Such a policy is served by
+   policy_fused_res_kernel<8> and, at batch <= small_batch, by one launch per layer
+   (replayed as a graph); opts.waves = 4 or 16 fails with GO2PI_E_INVALID for it, it has no
+   single-launch or resident kernel (resident_ms is accepted and go2pi_resident_kernel
+   reports "none"; ln_small and GO2PI_SKIP_SMALL have no effect on it), and
+   go2pi_controller_step* returns GO2PI_E_INVALID. go2pi_inspect_model reports each layer's
+   "res": the index of the layer whose carried value it adds, or -1.
    LayerNormalization (opset 17, over the feature axis, epsilon from the attribute, Scale
    and optional B constant, only output 0 used) is accepted on any dense layer but the last,
    once per layer: right after the layer's Gemm / MatMul (+ bias), in front of its
