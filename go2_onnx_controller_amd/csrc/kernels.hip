@@ -16,8 +16,9 @@
 //
 // 2. gemv_layer_kernel        — the small-batch (1..8 robots) latency path.
 //    One workgroup per 16-output tile, 8 waves split the K chunks, fp32 VALU
-//    dot products on the same packed fragments + wave/LDS reductions. One
-//    launch per layer, captured into a hipGraph by the engine.
+//    dot products on the same packed fragments + wave/LDS reductions
+//    (tile_layer.hpp states the order). One launch per layer, captured into a
+//    hipGraph by the engine.
 //
 // Numerics: fp32 storage and arithmetic throughout (the f32-input MFMA is an
 // exact k-ordered fmaf chain, no TF32/xf32 on gfx950). The summation order
@@ -26,15 +27,16 @@
 // identical instruction sequence wherever it sits in the batch: sharded and
 // unsharded runs are bit-identical.
 #include "fused_impl.hpp"
+#include "tile_layer.hpp"
 #include "w4ln_layout.hpp"
 
 namespace go2pi {
 
 // ---------------------------------------------------------------------------
 // Small-batch GEMV layer. grid = N_pad/16 workgroups (one per 16-output tile),
-// 8 waves split the K chunks. x: [B][x_stride] (device or host-mapped memory),
+// the tiled layer body of tile_layer.hpp. x: [B][x_stride] (device or host-mapped memory),
 // y: [B][y_stride]. Layer 0 applies the prologue; the final layer the epilogue.
-constexpr int GEMV_WAVES = lds::WAVES;
+constexpr int GEMV_WAVES = TILE_WAVES;
 
 // obs: the call's observation rows [B][in_dim] (the engine's staging buffer in a captured
 // graph: every replay reads the fresh rows), read by a layer with an observation skip input
@@ -55,37 +57,35 @@ __global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram 
   const DevLayer &L = P.L[layer];
   const int K_pad = L.K_pad, C = K_pad >> 4, T = L.N_pad >> 4;
   const int skip_n = L.skip_n;
-  const int *sidx = P.skip_idx[layer];
-  // the columns read from x (layer 0 with a gather: none, all of its columns come through sidx)
-  const int K = layer == 0 ? (skip_n ? 0 : P.in_dim) : P.L[layer - 1].N;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int t = blockIdx.x;
   const GemvLds LY = gemv_lds(K_pad);
   float *xs = reinterpret_cast<float *>(lds4), *part = xs + LY.xs.size;  // (the regions in LY's order)
   // Weights and bias do not depend on the input: issue their loads first so
-  // their latency overlaps the input staging (wave w owns chunks w, w+8, ...).
-  constexpr int MAXS = 8;  // chunk slots per wave: K_pad <= 8 * 8 * 16 = 1024 in registers
-  const float4 *W = reinterpret_cast<const float4 *>(L.w) + (size_t)t * 64 + lane;  // chunk-major
-  float4 wr[MAXS];
-#pragma unroll
-  for (int s = 0; s < MAXS; ++s) {
-    const int c = wave + s * GEMV_WAVES;
-    wr[s] = c < C ? W[(size_t)c * T * 64] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+  // their latency overlaps the input staging.
+  float4 wr[TILE_MAXS];
+  tile_load(wr, L.w, t, T, C, wave, lane);
   const float bv = (wave == 0 && lane < 16) ? L.bias[t * 16 + lane] : 0.f;
-  for (int e = tid; e < B * K_pad; e += GEMV_WAVES * 64) {
-    const int b = e / K_pad, k = e - b * K_pad;
-    float v = 0.f;
-    if (k < K) {
-      v = x[(size_t)b * x_stride + k];
-      if (layer == 0) v = prologue(P, v, k);
-    } else if (k < K + skip_n) {
-      // (the LN pass below normalises columns [0, K) by index and leaves these as they are)
-      const int c = sidx[k - K];
-      v = prologue(P, obs[(size_t)b * P.in_dim + c], c);
+  if (layer == 0 && skip_n) {
+    stage_gather(P, obs, P.in_dim, P.skip_idx[0], skip_n, xs, K_pad, B, tid);
+  } else if (layer == 0) {
+    stage_obs(P, x, x_stride, xs, K_pad, B, tid);
+  } else {  // the previous layer's K outputs from x, then this layer's skip columns
+    const int K = P.L[layer - 1].N;
+    const int *sidx = P.skip_idx[layer];
+    for (int e = tid; e < B * K_pad; e += GEMV_WAVES * 64) {
+      const int b = e / K_pad, k = e - b * K_pad;
+      float v = 0.f;
+      if (k < K) {
+        v = x[(size_t)b * x_stride + k];
+      } else if (k < K + skip_n) {
+        // (the LN pass below normalises columns [0, K) by index and leaves these as they are)
+        const int c = sidx[k - K];
+        v = prologue(P, obs[(size_t)b * P.in_dim + c], c);
+      }
+      xs[b * K_pad + k] = v;
     }
-    xs[b * K_pad + k] = v;
   }
   __syncthreads();
   // The previous layer's LayerNormalization (it stored its un-normalised output: a
@@ -95,58 +95,21 @@ __global__ __launch_bounds__(GEMV_WAVES * 64) void gemv_layer_kernel(DevProgram 
     ln_rows(xs, K_pad, wave, B, GEMV_WAVES, ln_of(P.L[layer - 1]), lane);
     __syncthreads();
   }
-  float p[GO2PI_SMALL_MAXB];
-#pragma unroll
-  for (int b = 0; b < GO2PI_SMALL_MAXB; ++b) p[b] = 0.f;
-  const int koff = (lane >> 4) << 2;
-  auto accumulate = [&](int c, const float4 &w) {
-#pragma unroll
-    for (int b = 0; b < GO2PI_SMALL_MAXB; ++b) {
-      if (b < B) {
-        const float4 a = *reinterpret_cast<const float4 *>(xs + b * K_pad + c * 16 + koff);
-        p[b] = fmaf(a.x, w.x, p[b]);
-        p[b] = fmaf(a.y, w.y, p[b]);
-        p[b] = fmaf(a.z, w.z, p[b]);
-        p[b] = fmaf(a.w, w.w, p[b]);
-      }
-    }
-  };
-#pragma unroll
-  for (int s = 0; s < MAXS; ++s) {
-    const int c = wave + s * GEMV_WAVES;
-    if (c < C) accumulate(c, wr[s]);
-  }
-  for (int c = wave + MAXS * GEMV_WAVES; c < C; c += GEMV_WAVES) accumulate(c, W[(size_t)c * T * 64]);
-#pragma unroll
-  for (int b = 0; b < GO2PI_SMALL_MAXB; ++b) {
-    p[b] += __shfl_xor(p[b], 16);
-    p[b] += __shfl_xor(p[b], 32);
-  }
-  if (lane < 16) {
-#pragma unroll
-    for (int b = 0; b < GO2PI_SMALL_MAXB; ++b)
-      if (b < B) part[(wave * GO2PI_SMALL_MAXB + b) * 16 + lane] = p[b];
-  }
+  // (chunks past the register slots, K_pad > 1024: their fragments from memory)
+  const float4 *W = reinterpret_cast<const float4 *>(L.w) + (size_t)t * 64 + lane;
+  tile_dot(xs, part, wr, K_pad, C, B, wave, lane, [&](int c) { return W[(size_t)c * T * 64]; });
   __syncthreads();
-  if (wave == 0 && lane < 16) {
-    const int n = t * 16 + lane;
-    const bool last = layer == P.nl - 1;
-    for (int b = 0; b < B; ++b) {
-      float s = 0.f;
-      for (int w2 = 0; w2 < GEMV_WAVES; ++w2) s += part[(w2 * GO2PI_SMALL_MAXB + b) * 16 + lane];
-      float sb = s + bv;
-      // (the carry buffers are cleared when the engine is built: a column no source wrote reads 0)
-      if (cin) sb += cin[(size_t)b * c_stride + n];
-      float v = act_fn(L.act, L.alpha, L.beta, sb);
-      if (last) {
-        if (n < L.N) y[(size_t)b * y_stride + n] = post_fn(P, v);
-      } else {
-        y[(size_t)b * y_stride + n] = v;  // padded columns are exact zeros
-        if (cout) cout[(size_t)b * c_stride + n] = v;
-      }
-    }
-  }
-  (void)T;
+  // (the carry buffers are cleared when the engine is built: a column no source wrote reads 0)
+  if (wave == 0 && lane < 16)
+    tile_finish(part, t, lane, B, bv, ActP{L.act, L.alpha, L.beta}, layer == P.nl - 1, cin, c_stride,
+                [&](int b, int n, float v, bool last) {
+                  if (last) {
+                    if (n < L.N) y[(size_t)b * y_stride + n] = post_fn(P, v);
+                  } else {
+                    y[(size_t)b * y_stride + n] = v;  // padded columns are exact zeros
+                    if (cout) cout[(size_t)b * c_stride + n] = v;
+                  }
+                });
 }
 
 // ---------------------------------------------------------------------------

@@ -17,7 +17,10 @@ polls or holds CUs beside the one being timed), legs alternated within a round, 
 rounds; per leg the median [min, max] over the rounds of each figure. With --touched the legs
 are instead the kernels this change's code sits beside, on this library and on copies of the
 parent's (--parent-lib, twice): ln_512_pre under ln_small = 1 and a plain 24 -> 600 -> 8
-policy (a layer input over 512 columns), single launch and resident.
+policy (a layer input over 512 columns): the general instantiations; go2_mlp_512 under
+GO2PI_RES_MULTI=1 (the plain ones: policy_latency_kernel, policy_resident_kernel<16, ...>) and
+go2_gru_256 (resident: the recurrent form; launched per call it runs the batched
+policy_gru_kernel, which such a change leaves alone: a control), single launch and resident.
 
   python3 tools/skip_small_ab.py --rounds 5 --parent-lib go2_onnx_controller_amd/lib/diag/libgo2pi_parent.so
 """
@@ -54,7 +57,10 @@ def child(args):
         wide = os.path.join(d, "plain_wide.onnx")
         with open(wide, "wb") as fh:
             fh.write(synth.mlp_model_bytes(**lm.PLAIN_WIDE))
-        models = {"ln_512_pre": (synth.ensure_model("ln_512_pre"), dict(ln_small=True)), "plain_600": (wide, {})}
+        # name -> (path, Engine keywords, switches set for that engine alone)
+        models = {"ln_512_pre": (synth.ensure_model("ln_512_pre"), dict(ln_small=True), ()), "plain_600": (wide, {}, ()),
+                  "go2_gru_256": (synth.ensure_model("go2_gru_256"), {}, ()),
+                  "go2_mlp_512": (synth.ensure_model("go2_mlp_512"), {}, ("GO2PI_RES_MULTI",))}
         res_ms = args.resident_ms if leg.startswith("resident") else 0
     else:
         models = {}
@@ -65,10 +71,14 @@ def child(args):
                     fh.write(synth.mlp_model_bytes(dims=PLAIN[name], seed=61, act="Elu"))
             else:
                 p = sm.model_path(name, d)
-            models[name] = (p, {})
+            models[name] = (p, {}, ())
         res_ms = args.resident_ms if leg in ("c", "d") else 0
-    for name, (path, kw) in models.items():
+    for name, (path, kw, switches) in models.items():
+        for sw in switches:  # (read at engine creation)
+            os.environ[sw] = "1"
         with Engine(path, max_batch=8, resident_ms=res_ms, **kw) as e:
+            for sw in switches:
+                del os.environ[sw]
             rng = np.random.default_rng(0)
             per = {}
             for B in BATCHES:
