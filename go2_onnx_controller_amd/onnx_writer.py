@@ -3,7 +3,7 @@
 `onnx` and `torch.onnx.export` are unavailable in this image, so
 the synthetic 48->512^3->12 MLP and GRU-256 policies that BASELINE.json's
 configs name are serialised here directly in the ModelProto wire format
-(field numbers as documented in go2_onnx_controller_amd/csrc/onnx_model.cpp).
+(field numbers as documented in go2_onnx_controller_amd/csrc/onnx_proto.hpp).
 The output is deterministic byte for byte.
 """
 from __future__ import annotations

@@ -10,54 +10,14 @@ model and of the loader-breadth graphs: truncations, bit flips, oversized varint
 (dims, lengths, field keys) and spliced byte runs. Every input must load or end in
 a clean exception (GO2PI_E_MODEL at the ABI); no crash, no sanitizer report.
 """
-import os
-import shutil
-import subprocess
-
 import numpy as np
-import pytest
 from hypothesis import HealthCheck, given, settings, strategies as st
 
 import graphs
-from conftest import ROOT, SHIPPED
-
-EXE = os.path.join(ROOT, "build", "fuzz_loader_asan")
-SRC = os.path.join(ROOT, "go2_onnx_controller_amd", "csrc")
-
-
-@pytest.fixture(scope="module")
-def harness():
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    os.makedirs(os.path.dirname(EXE), exist_ok=True)
-    subprocess.run(["g++", "-std=c++20", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", "-I" + SRC, os.path.join(ROOT, "tests", "cpp", "fuzz_loader.cpp"),
-                    os.path.join(SRC, "onnx_model.cpp"), "-o", EXE], check=True)
-    return EXE
-
-
-def _run(exe, paths):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe] + [str(p) for p in paths], capture_output=True, text=True, errors="replace", timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(paths)
-    return lines
-
+from conftest import SHIPPED
+from loader_harness import harness, run as _run, varint as _varint  # noqa: F401 (harness: a fixture)
 
 BASES = [open(SHIPPED, "rb").read()] + [graphs.variant_bytes(k, 3) for k in graphs.VARIANTS]
-
-
-def _varint(v):
-    out = bytearray()
-    while True:
-        b = v & 0x7F
-        v >>= 7
-        out.append(b | (0x80 if v else 0))
-        if not v:
-            return bytes(out)
 
 
 @st.composite

@@ -9,18 +9,15 @@ loader, the planner and the oracle; no device is touched.
 5. the integer probes: exactness bound, and every observation column and latent unit matters;
 6. the loader under AddressSanitizer / UBSan on the graphs and a few hundred mutations of each.
 """
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import graphs
 import ln_ref
 import skip_models as sm
-from conftest import ROOT, SHIPPED, abs_err
+from conftest import SHIPPED, abs_err
 from go2_onnx_controller_amd import onnx_writer as ow
+from loader_harness import harness, run as _run  # noqa: F401 (harness: a fixture)
 
 
 def _inspect(path):
@@ -253,42 +250,7 @@ def test_probe_is_exact_and_every_unit_matters(tmp_path, name):
             assert not np.array_equal(sm.probe_forward(name, x, zero=(l, j)), want), (l, j)
 
 
-# ---- 6. the loader under the sanitizers (a stand-alone program, as tests/test_cpu_fuzz.py builds it)
-@pytest.fixture(scope="module")
-def harness():
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    exe = os.path.join(ROOT, "build", "fuzz_loader_asan_skip")
-    src = os.path.join(ROOT, "go2_onnx_controller_amd", "csrc")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.run(["g++", "-std=c++20", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", "-I" + src, os.path.join(ROOT, "tests", "cpp", "fuzz_loader.cpp"),
-                    os.path.join(src, "onnx_model.cpp"), "-o", exe], check=True)
-    return exe
-
-
-def _run(exe, paths):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r =subprocess.run([exe] + [str(p) for p in paths], capture_output=True, text=True, errors="replace", timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(paths)
-    return lines
-
-
-def _varint(v):
-    v &= (1 << 64) - 1
-    out = bytearray()
-    while True:
-        b = v & 0x7F
-        v >>= 7
-        out.append(b | (0x80 if v else 0))
-        if not v:
-            return bytes(out)
-
-
+# ---- 6. the loader under the sanitizers (a stand-alone program, tests/loader_harness.py)
 def _mutations(name, n):
     """n mutations of the model: truncations, bit flips, and every Slice bound rewritten to a
     negative, huge or past-the-width value (the int64 initialisers' payloads and the
