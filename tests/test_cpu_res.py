@@ -1,10 +1,9 @@
-"""CPU: residual MLP policies (tests/res_models.py): what the loader reports (Dense::res), the
+"""CPU: residual MLP policies (the res family of tests/policy_specs.py): what the loader reports (Dense::res), the
 forms it refuses, the integer probes' own arithmetic, the input condition of the GPU tests
 (float32 alone stays under a third of the tolerance) and the plan (policy_fused_res_kernel<8>
 and the GEMV chain, nothing else), with the plan of policies without a residual pinned to the
 parent commit's (tests/golden/res_plan_parent.json).
 """
-import functools
 import json
 import os
 
@@ -14,8 +13,7 @@ import pytest
 import graphs
 import ln_ref
 import ln_small_models as lm
-import res_models as rm
-import skip_models as sm
+import policy_specs as ps
 from conftest import GOLDEN, SHIPPED, abs_err
 from go2_onnx_controller_amd import onnx_writer as ow
 
@@ -24,23 +22,12 @@ E_INVALID, E_MODEL = -1, -2  # include/go2pi.h
 KEYS = ("K", "N", "act", "ln", "skip", "res")
 
 
-@functools.lru_cache(maxsize=None)
-def _dir():
-    import tempfile
-    return tempfile.mkdtemp(prefix="res_models_")
-
-
-def _path(name):
-    return rm.model_path(name, _dir())
-
-
 # ---- 1. the loader's view
-@pytest.mark.parametrize("name", rm.NAMES + rm.PROBES)
+@pytest.mark.parametrize("name", ps.RES.names + ps.RES.probes)
 def test_inspect(name):
-    from go2_onnx_controller_amd import engine
-    v = engine.inspect_model(_path(name))
-    assert v["in_dim"] == rm.in_dim(name)
-    assert [{k: ly[k] for k in KEYS} for ly in v["layers"]] == rm.expected_view(name)
+    v = ps.inspect(ps.path(name))
+    assert v["in_dim"] == ps.in_dim(name)
+    assert [{k: ly[k] for k in KEYS} for ly in v["layers"]] == ps.expected_view(name)
 
 
 @pytest.mark.parametrize("kind", ["matmul_add_sigmoid", "relu_deep"])
@@ -160,47 +147,47 @@ def test_refusals(tmp_path, kind):
 
 
 # ---- 3. the probes' own arithmetic
-@pytest.mark.parametrize("name", rm.PROBES)
+@pytest.mark.parametrize("name", ps.RES.probes)
 def test_probe_forward_is_the_reference(name):
-    ref = ln_ref.LnRef(_path(name))
-    assert rm.probe_bound(name) < 2 ** 24
+    ref = ps.ref(name)
+    assert ps.probe_bound(name) < 2 ** 24
     for B in (33, 1, 16, 17, 8, 5):
-        x = rm.probe_obs(name, B)
-        want = rm.probe_forward(name, x)
+        x = ps.probe_obs(name, B)
+        want = ps.probe_forward(name, x)
         for y in (ref.f64(x), ref.f32(x)):
             assert np.array_equal(y, want.astype(y.dtype)) and np.array_equal(y.astype(np.int64), want)
 
 
-@pytest.mark.parametrize("name", rm.PROBES)
+@pytest.mark.parametrize("name", ps.RES.probes)
 def test_probe_observes_the_carried_path(name):
     """Zeroing any unit of a carried value on its way to the Add (the main chain keeps the
     unit) changes an output: a kernel that drops or misplaces the carried value is seen."""
-    _, layers = rm.spec(name)
-    x = rm.probe_obs(name, 33)
-    want = rm.probe_forward(name, x)
+    _, _, layers = ps.spec(name)
+    x = ps.probe_obs(name, 33)
+    want = ps.probe_forward(name, x)
     for l, ly in enumerate(layers):
         if ly["res"] is None:
             continue
         for j in range(ly["n"]):
-            assert not np.array_equal(rm.probe_forward(name, x, zero=(l, j)), want), (name, l, j)
+            assert not np.array_equal(ps.probe_forward(name, x, zero_carried=(l, j)), want), (name, l, j)
 
 
 # ---- 4. the input condition of tests/test_gpu_res.py
-@pytest.mark.parametrize("name", rm.NAMES)
+@pytest.mark.parametrize("name", ps.RES.names)
 def test_float32_alone_is_within_a_third_of_the_tolerance(name):
-    ref = ln_ref.LnRef(_path(name))
-    for B in rm.PARITY_BATCHES:
+    ref = ps.ref(name)
+    for B in ps.RES.parity_batches:
         for k in range(3 if B in (5, 33) else 1):
-            x = rm.obs(name, B, k)
+            x = ps.obs(name, B, k)
             err = abs_err(ref.f32(x), ref.f64(x))
             assert err <= TOL / 3, (name, B, k, err)
 
 
 # ---- 5. plan
-@pytest.mark.parametrize("name", rm.NAMES + rm.PROBES)
+@pytest.mark.parametrize("name", ps.RES.names + ps.RES.probes)
 def test_plan(name):
     from test_cpu_plan import plan
-    path = _path(name)
+    path = ps.path(name)
     for args, extra in (((), {}), (("GO2PI_SKIP_SMALL",), {"ln_small": 3}), ((), {"waves": 8})):
         got = plan(path, *args, resident_ms=100, **extra)
         assert got["batched_kernel"].startswith("policy_fused_res_kernel<8>"), got["batched_kernel"]
@@ -219,17 +206,17 @@ def test_plan_res_skip_consumer_is_padded_past_its_source():
     """res_skip: the consumer's N_pad (its skip successor's K_pad) exceeds the source's, so
     the carried tile has columns no source writes."""
     from test_cpu_plan import plan
-    got = plan(_path("res_skip"))
+    got = plan(ps.path("res_skip"))
     k_pad = [g["k_pad"] for g in got["lds"]["gemv"]]
     assert k_pad[3] == 64 and k_pad[5] == 128  # N_pad of layers 2 (the source) and 4 (the consumer)
 
 
 def test_plan_cost_counts_the_add():
     from test_cpu_plan import plan
-    _, layers = rm.spec("simba_64")
+    _, _, layers = ps.spec("simba_64")
     want = sum(2.0 * k * ly["n"] for k, ly in zip([48] + [ly["n"] for ly in layers[:-1]], layers))
     want += sum(ly["n"] for ly in layers if ly["res"] is not None)
-    assert plan(_path("simba_64"))["cost"]["flops_per_row"] == want
+    assert plan(ps.path("simba_64"))["cost"]["flops_per_row"] == want
 
 
 def _wide_bytes(width):
@@ -270,7 +257,7 @@ def parent_case_path(case, directory):
         return SHIPPED
     if case.startswith("ln_512_pre"):
         return lm.model_path("ln_512_pre", directory)
-    return sm.model_path("ea_98", directory)
+    return ps.model_path("ea_98", directory)
 
 
 @pytest.mark.parametrize("case", list(PARENT_CASES))

@@ -1,4 +1,4 @@
-"""CPU: estimator-actor policies (observation skip inputs, tests/skip_models.py) through the
+"""CPU: estimator-actor policies (observation skip inputs, the skip family of tests/policy_specs.py) through the
 loader, the planner and the oracle; no device is touched.
 
 1. the loader's view (inspect_model): K, N, act, ln and the skip columns per layer, and the
@@ -14,45 +14,40 @@ import pytest
 
 import graphs
 import ln_ref
-import skip_models as sm
+import policy_specs as ps
 from conftest import SHIPPED, abs_err
 from go2_onnx_controller_amd import onnx_writer as ow
 from loader_harness import harness, run as _run  # noqa: F401 (harness: a fixture)
 
 
-def _inspect(path):
-    from go2_onnx_controller_amd.engine import inspect_model
-    return inspect_model(str(path))
-
-
 # ---- 1. loader view
-@pytest.mark.parametrize("name", sm.NAMES + sm.PROBES)
+@pytest.mark.parametrize("name", ps.SKIP.names + ps.SKIP.probes)
 def test_loader_view(tmp_path, name):
-    v = _inspect(sm.model_path(name, tmp_path))
-    assert v["in_dim"] == sm.in_dim(name)
-    got = [{k: ly[k] for k in ("K", "N", "act", "ln", "skip")} for ly in v["layers"]]
-    assert got == sm.expected_view(name)
+    v = ps.inspect(ps.model_path(name, tmp_path))
+    assert v["in_dim"] == ps.in_dim(name)
+    got = [{k: ly[k] for k in ("K", "N", "act", "ln", "skip", "res")} for ly in v["layers"]]
+    assert got == ps.expected_view(name)
     # checksums are of the permuted W (device column order)
-    for ly, W, (_, b, _, _) in zip(v["layers"], sm.device_weights(name), sm.weights(name)):
+    for ly, W, (_, b, _, _) in zip(v["layers"], ps.device_weights(name), ps.weights(name)):
         s = 0.0
         for x in W.ravel():  # the loader's own order and precision: a double sum over [N][K]
             s += float(x)
         assert ly["w_sum"] == s
         assert ly["b_sum"] == float(np.sum(b.astype(np.float64)))
-    c = sm.front_constants(name)
-    assert v["pre_sub"] == (sm.in_dim(name) if c else 0) and v["pre_clip"] == ([-5.0, 5.0] if c else [-1e308, 1e308])
+    c = ps.front_constants(name)
+    assert v["pre_sub"] == (ps.in_dim(name) if c else 0) and v["pre_clip"] == ([-5.0, 5.0] if c else [-1e308, 1e308])
 
 
 def test_permutation_is_not_the_identity():
     """ea_k64 and ea_two put observation parts first: device order differs from ONNX order."""
     for name, l in (("ea_k64", 3), ("ea_two", 2), ("probe_k64", 2)):
-        assert not np.array_equal(sm.device_weights(name)[l], sm.weights(name)[l][0])
-    assert np.array_equal(sm.device_weights("ea_98")[3], sm.weights("ea_98")[3][0])
+        assert not np.array_equal(ps.device_weights(name)[l], ps.weights(name)[l][0])
+    assert np.array_equal(ps.device_weights("ea_98")[3], ps.weights("ea_98")[3][0])
 
 
 @pytest.mark.parametrize("kind", ["shipped", "slice_concat_blocks", "slice_concat_mixed"])
 def test_earlier_models_report_no_skip(tmp_path, kind):
-    v = _inspect(SHIPPED if kind == "shipped" else graphs.write(tmp_path, kind))
+    v = ps.inspect(SHIPPED if kind == "shipped" else graphs.write(tmp_path, kind))
     assert all(ly["skip"] == [] for ly in v["layers"]) and len(v["layers"]) >= 1
     if kind != "shipped":  # the front-end is still a prologue, layer 0 reads every column
         assert v["pre_sub"] > 1 or v["pre_div"] > 1 or v["pre_mul"] > 1
@@ -74,7 +69,7 @@ def test_held_scale_folds_into_the_running_columns_only(tmp_path):
              ow.node("Gemm", ["cat", "W1"], ["act"], "", [ow.attr_int("transB", 1)])]
     p = tmp_path / "held.onnx"
     p.write_bytes(ow.model(nodes, inits, [("obs", ["N", 8])], [("act", ["N", 3])]))
-    v = _inspect(p)
+    v = ps.inspect(p)
     assert v["layers"][1]["skip"] == [2, 3, 4, 5] and v["layers"][1]["K"] == 10
     want = np.concatenate([W1[:, 4:] * sc, W1[:, :4]], axis=1)  # device order, the scale on the first 6
     s = 0.0
@@ -185,7 +180,7 @@ def test_refusals(tmp_path, kind):
 @pytest.mark.parametrize("name", ["ea_98", "ea_k64"])
 def test_plan(tmp_path, name):
     from test_cpu_plan import plan
-    path = sm.model_path(name, tmp_path)
+    path = ps.model_path(name, tmp_path)
     for extra in ({}, {"ln_small": 3}):
         for waves, nw in ((0, 8), (4, 4), (8, 8), (16, 16)):
             got = plan(path, waves=waves, resident_ms=100, **extra)
@@ -196,7 +191,7 @@ def test_plan(tmp_path, name):
             assert got["latency_ok"] == 0 and got["w4_tpw"] == 0
     got = plan(path, resident_ms=100)
     cost = got["cost"]
-    view = sm.expected_view(name)
+    view = ps.expected_view(name)
     assert cost["flops_per_row"] == sum(2.0 * ly["K"] * ly["N"] for ly in view)  # the layers' real K
     assert cost["weight_bytes"] == sum(4.0 * (ly["K"] * ly["N"] + ly["N"]) for ly in view)
     # the skip layer's K_pad = ceil64(prev.N + skip_n), the layer in front padded to it
@@ -208,46 +203,46 @@ def test_plan(tmp_path, name):
 def test_plan_head_fuse(tmp_path):
     from test_cpu_plan import plan
     # a skip on the head itself: no head fusion; on the layer in front of the head: as ever
-    assert plan(sm.model_path("ea_head", tmp_path))["head_fuse"] == 0
-    assert plan(sm.model_path("ea_sig", tmp_path), waves=4)["head_fuse"] == 1
+    assert plan(ps.model_path("ea_head", tmp_path))["head_fuse"] == 0
+    assert plan(ps.model_path("ea_sig", tmp_path), waves=4)["head_fuse"] == 1
 
 
 # ---- 4. the oracle's own float32 error on the GPU tests' inputs
-@pytest.mark.parametrize("name", sm.NAMES)
+@pytest.mark.parametrize("name", ps.SKIP.names)
 def test_input_condition(tmp_path, name):
-    ref = ln_ref.LnRef(sm.model_path(name, tmp_path))
+    ref = ln_ref.LnRef(ps.model_path(name, tmp_path))
     worst = 0.0
-    for B in sm.PARITY_BATCHES:
+    for B in ps.SKIP.parity_batches:
         for k in (0, 1):
-            x = sm.obs(name, B, k)
+            x = ps.obs(name, B, k)
             worst = max(worst, abs_err(ref.f32(x), ref.f64(x)))
     print(f"{name}: worst fp32-vs-fp64 error {worst:.3g}")
     assert worst <= 1e-5 / 3
-    c = sm.front_constants(name)
+    c = ps.front_constants(name)
     if c:  # the front's Clip binds on both sides
-        v = (sm.obs(name, 33) - c[0]) / c[1]
+        v = (ps.obs(name, 33) - c[0]) / c[1]
         assert (v < -c[2]).any() and (v > c[2]).any()
 
 
 # ---- 5. probes
-@pytest.mark.parametrize("name", sm.PROBES)
+@pytest.mark.parametrize("name", ps.SKIP.probes)
 def test_probe_is_exact_and_every_unit_matters(tmp_path, name):
-    bound = sm.probe_bound(name)
+    bound = ps.probe_bound(name)
     print(f"{name}: largest sum |w||h| + |b| = {bound} (2^24 = {1 << 24})")
     assert bound < 1 << 24
-    ref = ln_ref.LnRef(sm.model_path(name, tmp_path))
-    x = sm.probe_obs(name, 33)
-    want = sm.probe_forward(name, x)
+    ref = ln_ref.LnRef(ps.model_path(name, tmp_path))
+    x = ps.probe_obs(name, 33)
+    want = ps.probe_forward(name, x)
     for dt in (np.float64, np.float32):  # the oracle agrees with the int64 answer, exactly
         y = ref._act(x, dt)
         assert np.array_equal(y, want.astype(dt)), dt
     assert np.abs(want).max() <= bound
-    _, _, layers = sm.PROBE_SPECS[name]
-    for j in range(sm.in_dim(name)):
-        assert not np.array_equal(sm.probe_forward(name, x, zero=(-1, j)), want), ("obs", j)
+    _, _, layers = ps.spec(name)
+    for j in range(ps.in_dim(name)):
+        assert not np.array_equal(ps.probe_forward(name, x, zero_unit=(-1, j)), want), ("obs", j)
     for l, ly in enumerate(layers[:-1]):
         for j in range(ly["n"]):
-            assert not np.array_equal(sm.probe_forward(name, x, zero=(l, j)), want), (l, j)
+            assert not np.array_equal(ps.probe_forward(name, x, zero_unit=(l, j)), want), (l, j)
 
 
 # ---- 6. the loader under the sanitizers (a stand-alone program, tests/loader_harness.py)
@@ -255,10 +250,10 @@ def _mutations(name, n):
     """n mutations of the model: truncations, bit flips, and every Slice bound rewritten to a
     negative, huge or past-the-width value (the int64 initialisers' payloads and the
     attribute-form varints)."""
-    data = sm.model_bytes(name)
-    rng = np.random.default_rng(sm.SEED[name] + 7)
+    data = ps.model_bytes(name)
+    rng = np.random.default_rng(ps.weight_seed(name) + 7)
     out = []
-    bounds = [-1, -3, -(1 << 40), -(1 << 63), (1 << 63) - 1, 1 << 40, (1 << 31) - 1, sm.in_dim(name) + 1, 0, 1 << 31]
+    bounds = [-1, -3, -(1 << 40), -(1 << 63), (1 << 63) - 1, 1 << 40, (1 << 31) - 1, ps.in_dim(name) + 1, 0, 1 << 31]
     # the Slice bounds stored as int64 raw_data: an 8-byte little-endian payload behind "st<k>" / "en<k>"
     spots = []
     for key in (b"st", b"en"):
@@ -289,10 +284,10 @@ def _mutations(name, n):
 
 def test_loader_sanitized(harness, tmp_path):
     paths, n_valid = [], 0
-    for name in sm.NAMES:
-        paths.append(sm.model_path(name, tmp_path))
+    for name in ps.SKIP.names:
+        paths.append(ps.model_path(name, tmp_path))
         n_valid += 1
-    for name in sm.NAMES:
+    for name in ps.SKIP.names:
         for i, d in enumerate(_mutations(name, 300)):
             p = tmp_path / f"{name}_m{i}.onnx"
             p.write_bytes(d)

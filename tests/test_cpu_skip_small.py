@@ -16,7 +16,7 @@ import pytest
 
 import ln_ref
 import ln_small_models as lm
-import skip_small_models as ssm
+import policy_specs as ps
 from conftest import SHIPPED, abs_err
 from test_cpu_lds_layout import check_regions
 from test_cpu_plan import plan
@@ -33,9 +33,9 @@ def _opts(name):
 
 
 # ---- 1. with the switch
-@pytest.mark.parametrize("name", ssm.NAMES + ssm.PROBES)
+@pytest.mark.parametrize("name", ps.SMALL_NAMES + ps.SMALL_PROBES)
 def test_selection_with_the_switch(tmp_path, name):
-    path = ssm.model_path(name, tmp_path)
+    path = ps.model_path(name, tmp_path)
     got = plan(path, SW, resident_ms=100, **_opts(name))
     off = plan(path, resident_ms=100, **_opts(name))
     assert got["small_kernel"] == "policy_latency_kernel"
@@ -56,7 +56,7 @@ def test_selection_with_the_switch(tmp_path, name):
 
 
 def test_ln_skip_needs_the_ln_small_bit_too(tmp_path):
-    path = ssm.model_path("ea_ln", tmp_path)
+    path = ps.model_path("ea_ln", tmp_path)
     for extra in ({}, {"ln_small": 2}):
         got = plan(path, SW, resident_ms=100, **extra)
         assert got["small_kernel"] == CHAIN and got["resident_kernel"] == "none" and got["latency_ok"] == 0
@@ -68,19 +68,19 @@ def test_ln_skip_needs_the_ln_small_bit_too(tmp_path):
 def test_local_layer0_and_gather_geometry(tmp_path):
     """probe_local0 runs the local layer 0 with NF = 8; probe_gather0 has the same layer-0
     geometry and a gather, so it is tiled; GO2PI_RES_TILED0 tiles both."""
-    a = plan(ssm.model_path("probe_local0", tmp_path), SW, resident_ms=100)["lds"]
-    b = plan(ssm.model_path("probe_gather0", tmp_path), SW, resident_ms=100)["lds"]
+    a = plan(ps.model_path("probe_local0", tmp_path), SW, resident_ms=100)["lds"]
+    b = plan(ps.model_path("probe_gather0", tmp_path), SW, resident_ms=100)["lds"]
     assert (a["k0_pad"], a["n0_pad"], a["act"]["nf"]) == (128, 128, 8)
     assert (b["k0_pad"], b["n0_pad"], b["act"]["nf"]) == (128, 128, 0)
-    assert plan(ssm.model_path("probe_local0", tmp_path), SW, "GO2PI_RES_TILED0", resident_ms=100)["lds"]["act"]["nf"] == 0
-    r2 = plan(ssm.model_path("ea_round2", tmp_path), SW, resident_ms=100)
+    assert plan(ps.model_path("probe_local0", tmp_path), SW, "GO2PI_RES_TILED0", resident_ms=100)["lds"]["act"]["nf"] == 0
+    r2 = plan(ps.model_path("ea_round2", tmp_path), SW, resident_ms=100)
     assert r2["one_round"] == 0 and max(g["k_pad"] for g in r2["lds"]["gemv"][1:]) == 640
 
 
 # ---- 2. the switch beside other settings
 @pytest.mark.parametrize("name", ["ea_98", "ea_k64", "probe_gather0"])
 def test_switch_with_other_settings(tmp_path, name):
-    path = ssm.model_path(name, tmp_path)
+    path = ps.model_path(name, tmp_path)
     got = plan(path, SW, "GO2PI_SMALL_CHAIN", resident_ms=100)
     assert got["small_kernel"] == CHAIN and got["resident_kernel"] == "none" and got["latency_ok"] == 0
     assert plan(path, SW, small_batch=-1, resident_ms=100) == plan(path, small_batch=-1, resident_ms=100)
@@ -111,11 +111,11 @@ def test_plain_wide_layer_keeps_its_plan(tmp_path):
 
 # ---- 4. LDS regions
 @pytest.mark.parametrize("tiled0", [False, True])
-@pytest.mark.parametrize("name", ssm.NAMES + ssm.PROBES)
+@pytest.mark.parametrize("name", ps.SMALL_NAMES + ps.SMALL_PROBES)
 def test_lds_regions(tmp_path, name, tiled0):
     sw = [SW] + (["GO2PI_RES_TILED0"] if tiled0 else [])
-    lds = plan(ssm.model_path(name, tmp_path), *sw, resident_ms=100, **_opts(name))["lds"]
-    view = ssm.expected_view(name)
+    lds = plan(ps.model_path(name, tmp_path), *sw, resident_ms=100, **_opts(name))["lds"]
+    view = ps.expected_view(name)
     kmax = max((ly["K"] + 63) // 64 * 64 for ly in view)
     for key in ("latency", "act"):
         f = lds[key]
@@ -124,52 +124,51 @@ def test_lds_regions(tmp_path, name, tiled0):
         size = {n: s for n, _, s in f["regions"]}
         assert size["xs"] >= 8 * kmax  # eight rows of the widest layer input, skip columns included
         if key == "act":
-            assert size["obsv"] >= 8 * ssm.in_dim(name)  # the raw rows a skip layer reads
+            assert size["obsv"] >= 8 * ps.in_dim(name)  # the raw rows a skip layer reads
 
 
 # ---- 5. the probes and the float model's input condition
-@pytest.mark.parametrize("name", ssm.NEW_PROBES)
+@pytest.mark.parametrize("name", ps.SKIP_SMALL.probes)
 def test_probe_is_exact_and_every_unit_matters(tmp_path, name):
-    bound = ssm.probe_bound(name)
+    bound = ps.probe_bound(name)
     print(f"{name}: largest sum |w||h| + |b| = {bound} (2^24 = {1 << 24})")
     assert bound < 1 << 24
-    ref = ln_ref.LnRef(ssm.model_path(name, tmp_path))
-    for B in (33,) + tuple(sorted(set(ssm.PROBE_BATCHES))):
-        x = ssm.probe_obs(name, B)
-        want = ssm.probe_forward(name, x)
+    ref = ln_ref.LnRef(ps.model_path(name, tmp_path))
+    for B in (33,) + tuple(sorted(set(ps.SKIP_SMALL.probe_batches))):
+        x = ps.probe_obs(name, B)
+        want = ps.probe_forward(name, x)
         for dt in (np.float64, np.float32):  # the oracle agrees with the int64 answer, exactly
             assert np.array_equal(ref._act(x, dt), want.astype(dt)), (B, dt)
         assert np.abs(want).max() <= bound
-    x = ssm.probe_obs(name, 33)
-    want = ssm.probe_forward(name, x)
-    _, _, layers = ssm.PROBE_SPECS[name]
-    assert ssm.read_columns(name) == list(range(ssm.in_dim(name)))
-    for j in range(ssm.in_dim(name)):
-        assert not np.array_equal(ssm.probe_forward(name, x, zero=(-1, j)), want), ("obs", j)
+    x = ps.probe_obs(name, 33)
+    want = ps.probe_forward(name, x)
+    _, _, layers = ps.spec(name)
+    assert ps.read_columns(name) == list(range(ps.in_dim(name)))
+    for j in range(ps.in_dim(name)):
+        assert not np.array_equal(ps.probe_forward(name, x, zero_unit=(-1, j)), want), ("obs", j)
     for l, ly in enumerate(layers[:-1]):
         for j in range(ly["n"]):
-            assert not np.array_equal(ssm.probe_forward(name, x, zero=(l, j)), want), (l, j)
+            assert not np.array_equal(ps.probe_forward(name, x, zero_unit=(l, j)), want), (l, j)
 
 
 def test_input_condition_of_the_new_float_model(tmp_path):
     """ea_round2 on the inputs tests/test_gpu_skip_small.py uses: float32 arithmetic alone
     stays under a third of the tolerance."""
     name = "ea_round2"
-    ref = ln_ref.LnRef(ssm.model_path(name, tmp_path))
+    ref = ln_ref.LnRef(ps.model_path(name, tmp_path))
     worst = 0.0
-    for B in ssm.SMALL_BATCHES:
+    for B in ps.SKIP_SMALL.small_batches:
         for k in (0, 1):
-            x = ssm.obs(name, B, k)
+            x = ps.obs(name, B, k)
             worst = max(worst, abs_err(ref.f32(x), ref.f64(x)))
     print(f"{name}: worst fp32-vs-fp64 error {worst:.3g}")
     assert worst <= 1e-5 / 3
 
 
 # ---- 6. loader view
-@pytest.mark.parametrize("name", ssm.NEW_NAMES + ssm.NEW_PROBES)
+@pytest.mark.parametrize("name", ps.SKIP_SMALL.names + ps.SKIP_SMALL.probes)
 def test_loader_view(tmp_path, name):
-    from go2_onnx_controller_amd.engine import inspect_model
-    v = inspect_model(ssm.model_path(name, tmp_path))
-    assert v["in_dim"] == ssm.in_dim(name)
-    got = [{k: ly[k] for k in ("K", "N", "act", "ln", "skip")} for ly in v["layers"]]
-    assert got == ssm.expected_view(name)
+    v = ps.inspect(ps.model_path(name, tmp_path))
+    assert v["in_dim"] == ps.in_dim(name)
+    got = [{k: ly[k] for k in ("K", "N", "act", "ln", "skip", "res")} for ly in v["layers"]]
+    assert got == ps.expected_view(name)

@@ -1,18 +1,16 @@
-"""GPU: residual MLP policies (tests/res_models.py) on the two kernels that serve them: the
+"""GPU: residual MLP policies (the res family of tests/policy_specs.py) on the two kernels that serve them: the
 general batched body with a carried tile (policy_fused_res_kernel<8>, fused_impl.hpp RES) and
 the GEMV chain with its carry buffers (gemv_layer_kernel), against the float64 reference at
 the project's 1e-5 and, for the integer probes, exactly. tests/test_cpu_res.py checks on the
 same inputs that float32 arithmetic alone stays under a third of the tolerance.
 """
-import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-import ln_ref
-import res_models as rm
+import policy_specs as ps
 from conftest import abs_err
 
 pytestmark = pytest.mark.gpu
@@ -22,64 +20,42 @@ GEMV = "gemv_layer_kernel graph"
 BODY = "policy_fused_res_kernel<8>"
 
 
-@functools.lru_cache(maxsize=None)
-def _dir():
-    import tempfile
-    return tempfile.mkdtemp(prefix="res_models_")
-
-
-def _path(name):
-    return rm.model_path(name, _dir())
-
-
-@functools.lru_cache(maxsize=None)
-def _ref(name):
-    return ln_ref.LnRef(_path(name))
-
-
-@functools.lru_cache(maxsize=None)
-def _want(name, B, k=0):
-    y = _ref(name).f64(rm.obs(name, B, k))
-    y.setflags(write=False)
-    return y
-
-
 def _engine(name, **kw):
     from go2_onnx_controller_amd import Engine
     kw.setdefault("max_batch", 128)
-    return Engine(_path(name), **kw)
+    return Engine(ps.path(name), **kw)
 
 
 # ---- 1. parity
-@pytest.mark.parametrize("name", rm.NAMES)
+@pytest.mark.parametrize("name", ps.RES.names)
 def test_parity(name):
     with _engine(name, resident_ms=100) as e:
         assert e.batched_kernel.startswith(BODY), e.batched_kernel
         assert e.small_kernel == GEMV
         assert e.resident_kernel.startswith("none"), e.resident_kernel
-        assert e.in_dim == rm.in_dim(name)
-        for B in rm.PARITY_BATCHES:
-            err = abs_err(e.run(rm.obs(name, B)), _want(name, B))
+        assert e.in_dim == ps.in_dim(name)
+        for B in ps.RES.parity_batches:
+            err = abs_err(e.run(ps.obs(name, B)), ps.want(name, B))
             print(f"{name} B={B}: {err:.3g}")
             assert err <= TOL, (name, B, err)
 
 
 # ---- 2. the probes, exactly
-@pytest.mark.parametrize("name", rm.PROBES)
+@pytest.mark.parametrize("name", ps.RES.probes)
 def test_probes_exact(name):
     with _engine(name, small_batch=-1) as e:  # the body at every batch
         assert e.small_kernel.startswith(BODY)
         for B in (33, 1, 16, 17):
-            x = rm.probe_obs(name, B)
+            x = ps.probe_obs(name, B)
             got = e.run(x)
-            assert np.array_equal(got, np.rint(got)) and np.array_equal(got.astype(np.int64), rm.probe_forward(name, x)), \
+            assert np.array_equal(got, np.rint(got)) and np.array_equal(got.astype(np.int64), ps.probe_forward(name, x)), \
                 (name, "body", B)
     with _engine(name) as e:  # the chain
         assert e.small_kernel == GEMV
         for B in (8, 1, 5):
-            x = rm.probe_obs(name, B)
+            x = ps.probe_obs(name, B)
             got = e.run(x)
-            assert np.array_equal(got, np.rint(got)) and np.array_equal(got.astype(np.int64), rm.probe_forward(name, x)), \
+            assert np.array_equal(got, np.rint(got)) and np.array_equal(got.astype(np.int64), ps.probe_forward(name, x)), \
                 (name, "chain", B)
 
 
@@ -89,10 +65,10 @@ def test_graph_replay(name):
     with _engine(name) as e:
         assert e.small_kernel == GEMV
         for B in (1, 5):
-            xs = [rm.obs(name, B, k) for k in (0, 1, 0)]
+            xs = [ps.obs(name, B, k) for k in (0, 1, 0)]
             ys = [e.run(x) for x in xs]
             for k, y in zip((0, 1, 0), ys):
-                assert abs_err(y, _want(name, B, k)) <= TOL, (name, B, k)
+                assert abs_err(y, ps.want(name, B, k)) <= TOL, (name, B, k)
             assert np.array_equal(ys[0], ys[2]) and not np.array_equal(ys[0], ys[1])
 
 
@@ -102,7 +78,7 @@ def test_graph_replay(name):
 def test_nan_stays_in_its_row(name, B):
     """The rows beside a NaN row equal the clean run bit for bit: garbage in the carried
     tile or in a carry buffer would move them."""
-    x = rm.obs(name, B)
+    x = ps.obs(name, B)
     with _engine(name) as e:
         clean = e.run(x)
         bad = x.copy()
@@ -124,16 +100,16 @@ def test_clean_pads(name, B):
     Twice, each time on a fresh engine."""
     for _ in range(2):
         with _engine(name) as e:
-            y = e.run(rm.obs(name, B))
+            y = e.run(ps.obs(name, B))
         assert np.isfinite(y).all()
-        assert abs_err(y, _want(name, B)) <= TOL
+        assert abs_err(y, ps.want(name, B)) <= TOL
 
 
 # ---- 6. device sequence
 def test_sequence_equals_single_runs():
     import torch
     name, B, T = "simba_64", 33, 3
-    xs = np.stack([rm.obs(name, B, k) for k in range(T)])
+    xs = np.stack([ps.obs(name, B, k) for k in range(T)])
     with _engine(name) as e:
         xd = torch.from_numpy(xs).cuda()
         seq = e.run_sequence_torch(xd)
@@ -142,14 +118,14 @@ def test_sequence_equals_single_runs():
     seq, single = seq.cpu().numpy(), single.cpu().numpy()
     assert np.array_equal(seq, single)
     for t in range(T):
-        assert abs_err(seq[t], _want(name, B, t)) <= TOL
+        assert abs_err(seq[t], ps.want(name, B, t)) <= TOL
     assert not np.array_equal(seq[0], seq[1])
 
 
 # ---- 7. shards and repeats
 @pytest.mark.parametrize("name", ["simba_256", "res_v1"])
 def test_shards_and_repeats_bitwise(name):
-    x = rm.obs(name, 33)
+    x = ps.obs(name, 33)
     with _engine(name) as e:
         whole = e.run(x)
         again = e.run(x)
@@ -165,14 +141,14 @@ def test_python_onnx_actor():
     from go2_onnx_controller_amd import ONNXActor
     name = "simba_64"
     obs, act = np.zeros(48, np.float32), np.zeros(12, np.float32)
-    actor = ONNXActor(_path(name), obs, act)
+    actor = ONNXActor(ps.path(name), obs, act)
     assert actor.check_dims()
-    x = rm.obs(name, 5)
+    x = ps.obs(name, 5)
     seen = []
     for i in (0, 1, 0):
         obs[:] = x[i]
         actor.act()
-        assert abs_err(act, _want(name, 5)[i]) <= TOL, i
+        assert abs_err(act, ps.want(name, 5)[i]) <= TOL, i
         seen.append(act.copy())
     assert not np.array_equal(seen[0], seen[1]) and np.array_equal(seen[0], seen[2])
 
@@ -184,7 +160,7 @@ def test_cpp_onnx_actor_ticks(resident, tmp_path):
     from test_cpu_boundary import build_controller_shape
     exe = build_controller_shape()
     dump, ticks = tmp_path / "actions.bin", 60
-    r = subprocess.run([exe, _path("res_skip"), "ticks", str(ticks), str(dump)], capture_output=True, text=True,
+    r = subprocess.run([exe, ps.path("res_skip"), "ticks", str(ticks), str(dump)], capture_output=True, text=True,
                        timeout=120, env=dict(os.environ, GO2PI_RESIDENT_MS=resident))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "check_dims: 1" in r.stdout
@@ -193,7 +169,7 @@ def test_cpp_onnx_actor_ticks(resident, tmp_path):
     for t in range(ticks):
         o[t % 98] += np.float32(0.001)
         seq[t] = o
-    assert abs_err(got, _ref("res_skip").f64(seq)) <= TOL
+    assert abs_err(got, ps.ref("res_skip").f64(seq)) <= TOL
     assert len(np.unique(got[:, 0])) > ticks // 2
 
 
@@ -209,11 +185,11 @@ def test_controller_step_is_refused():
             obs, act = np.zeros((B, 98), np.float32), np.zeros((B, 12), np.float32)
             with pytest.raises(Go2piError, match="the controller tick does not serve a policy with residual connections"):
                 e.controller_step(st, obs, act, joy=joy)
-        assert abs_err(e.run(rm.obs(name, 5)), _want(name, 5)) <= TOL  # the engine still serves run()
+        assert abs_err(e.run(ps.obs(name, 5)), ps.want(name, 5)) <= TOL  # the engine still serves run()
 
 
 def test_explicit_waves_are_refused():
     from go2_onnx_controller_amd import Engine, Go2piError
     for waves in (4, 16):
         with pytest.raises(Go2piError, match="residual connections"):
-            Engine(_path("simba_64"), max_batch=8, waves=waves)
+            Engine(ps.path("simba_64"), max_batch=8, waves=waves)

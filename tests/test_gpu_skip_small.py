@@ -6,18 +6,15 @@ same inputs that float32 arithmetic alone stays under a third of the tolerance.
 
 The switch is read when an engine is created, so every test sets it first.
 """
-import functools
 import os
 import subprocess
-import tempfile
 import time
 import warnings
 
 import numpy as np
 import pytest
 
-import ln_ref
-import skip_small_models as ssm
+import policy_specs as ps
 from conftest import abs_err
 
 pytestmark = pytest.mark.gpu
@@ -30,27 +27,6 @@ MULTI = "policy_resident_kernel"
 FORMS = ("launch", "resident")
 
 
-@functools.lru_cache(maxsize=None)
-def _dir():
-    return tempfile.mkdtemp(prefix="skip_small_models_")
-
-
-def _path(name):
-    return ssm.model_path(name, _dir())
-
-
-@functools.lru_cache(maxsize=None)
-def _ref(name):
-    return ln_ref.LnRef(_path(name))
-
-
-@functools.lru_cache(maxsize=None)
-def _want(name, B, k=0):
-    y = _ref(name).f64(ssm.obs(name, B, k))
-    y.setflags(write=False)
-    return y
-
-
 def _engine(name, form, **kw):
     """An engine created under the switch (the caller has set it): the single launch, or the
     resident kernel."""
@@ -58,7 +34,7 @@ def _engine(name, form, **kw):
     kw.setdefault("max_batch", 8)
     if name == "ea_ln":
         kw.setdefault("ln_small", True)
-    e = Engine(_path(name), resident_ms=RES_MS if form == "resident" else 0, **kw)
+    e = Engine(ps.path(name), resident_ms=RES_MS if form == "resident" else 0, **kw)
     assert e.small_kernel == LATENCY, e.small_kernel
     if form == "resident":
         assert e.resident_kernel.startswith(MULTI + " ring="), e.resident_kernel
@@ -75,26 +51,26 @@ def _served_by(e, form):
 def test_selection(monkeypatch):
     from go2_onnx_controller_amd import Engine
     monkeypatch.delenv(SW, raising=False)
-    with Engine(_path("ea_98"), max_batch=8, resident_ms=RES_MS) as e:  # as tests/test_gpu_skip.py pins it
+    with Engine(ps.path("ea_98"), max_batch=8, resident_ms=RES_MS) as e:  # as tests/test_gpu_skip.py pins it
         assert e.small_kernel == "gemv_layer_kernel graph" and e.resident_kernel.startswith("none")
     monkeypatch.setenv(SW, "1")
-    with Engine(_path("ea_98"), max_batch=64, resident_ms=RES_MS) as e:
+    with Engine(ps.path("ea_98"), max_batch=64, resident_ms=RES_MS) as e:
         assert e.small_kernel == LATENCY
         assert e.resident_kernel.startswith(MULTI + " ring="), e.resident_kernel
         assert e.batched_kernel.startswith("policy_fused_kernel<8, 0, 0, 0, 0,")
-        assert abs_err(e.run(ssm.obs("ea_98", 33)), _ref("ea_98").f64(ssm.obs("ea_98", 33))) <= TOL  # the batched body
-        assert abs_err(e.run(ssm.obs("ea_98", 5)), _want("ea_98", 5)) <= TOL
+        assert abs_err(e.run(ps.obs("ea_98", 33)), ps.ref("ea_98").f64(ps.obs("ea_98", 33))) <= TOL  # the batched body
+        assert abs_err(e.run(ps.obs("ea_98", 5)), ps.want("ea_98", 5)) <= TOL
 
 
 # ---- 2. parity
 @pytest.mark.parametrize("form", FORMS)
-@pytest.mark.parametrize("name", ssm.NAMES)
+@pytest.mark.parametrize("name", ps.SMALL_NAMES)
 def test_parity(name, form, monkeypatch):
     monkeypatch.setenv(SW, "1")
     with _engine(name, form) as e:
-        for B in ssm.SMALL_BATCHES:
-            y = e.run(ssm.obs(name, B))
-            err = abs_err(y, _want(name, B))
+        for B in ps.SKIP_SMALL.small_batches:
+            y = e.run(ps.obs(name, B))
+            err = abs_err(y, ps.want(name, B))
             print(f"{name} {form} B={B}: {err:.3g}")
             assert np.isfinite(y).all() and err <= TOL, (name, form, B, err)
         _served_by(e, form)
@@ -108,8 +84,8 @@ def test_parity_resident_variants(name, env, monkeypatch):
     with _engine(name, "resident") as e:
         if env == "GO2PI_REQ_HOST":
             assert e.resident_kernel.endswith("ring=host")
-        for B in ssm.SMALL_BATCHES:
-            err = abs_err(e.run(ssm.obs(name, B)), _want(name, B))
+        for B in ps.SKIP_SMALL.small_batches:
+            err = abs_err(e.run(ps.obs(name, B)), ps.want(name, B))
             print(f"{name} {env} B={B}: {err:.3g}")
             assert err <= TOL, (name, env, B, err)
         _served_by(e, "resident")
@@ -117,15 +93,15 @@ def test_parity_resident_variants(name, env, monkeypatch):
 
 # ---- 3. the probes, exactly, in an order that would show a stale row of a larger request
 @pytest.mark.parametrize("form", FORMS)
-@pytest.mark.parametrize("name", ssm.PROBES)
+@pytest.mark.parametrize("name", ps.SMALL_PROBES)
 def test_probes_exact(name, form, monkeypatch):
     monkeypatch.setenv(SW, "1")
     with _engine(name, form) as e:
-        for B in ssm.PROBE_BATCHES:
-            x = ssm.probe_obs(name, B)
+        for B in ps.SKIP_SMALL.probe_batches:
+            x = ps.probe_obs(name, B)
             got = e.run(x)
             assert np.array_equal(got, np.rint(got)), (name, form, B)
-            assert np.array_equal(got.astype(np.int64), ssm.probe_forward(name, x)), (name, form, B)
+            assert np.array_equal(got.astype(np.int64), ps.probe_forward(name, x)), (name, form, B)
         _served_by(e, form)
 
 
@@ -134,9 +110,9 @@ def test_probe_local0_tiled(monkeypatch):
     monkeypatch.setenv(SW, "1")
     monkeypatch.setenv("GO2PI_RES_TILED0", "1")
     with _engine("probe_local0", "resident") as e:
-        for B in ssm.PROBE_BATCHES:
-            x = ssm.probe_obs("probe_local0", B)
-            assert np.array_equal(e.run(x).astype(np.int64), ssm.probe_forward("probe_local0", x)), B
+        for B in ps.SKIP_SMALL.probe_batches:
+            x = ps.probe_obs("probe_local0", B)
+            assert np.array_equal(e.run(x).astype(np.int64), ps.probe_forward("probe_local0", x)), B
         _served_by(e, "resident")
 
 
@@ -147,13 +123,13 @@ def test_second_request_reads_its_own_skip_columns(form, kw, monkeypatch):
     obs[0:49] alone differ through the skip alone."""
     monkeypatch.setenv(SW, "1")
     name = "ea_l0slice"
-    a = ssm.obs(name, 5)
+    a = ps.obs(name, 5)
     b = a.copy()
-    b[:, :49] = ssm.obs(name, 5, 1)[:, :49]
+    b[:, :49] = ps.obs(name, 5, 1)[:, :49]
     with _engine(name, form, **kw) as e:
         ya, yb, ya2 = e.run(a), e.run(b), e.run(a)
         _served_by(e, form)
-    assert abs_err(ya, _ref(name).f64(a)) <= TOL and abs_err(yb, _ref(name).f64(b)) <= TOL
+    assert abs_err(ya, ps.ref(name).f64(a)) <= TOL and abs_err(yb, ps.ref(name).f64(b)) <= TOL
     assert not np.array_equal(ya, yb) and np.array_equal(ya, ya2)
 
 
@@ -162,7 +138,7 @@ def test_second_request_reads_its_own_skip_columns(form, kw, monkeypatch):
 def test_nan_in_a_skip_only_column_stays_in_its_row(form, monkeypatch):
     monkeypatch.setenv(SW, "1")
     name, B = "ea_l0slice", 5
-    x = ssm.obs(name, B)
+    x = ps.obs(name, B)
     bad = x.copy()
     bad[2, 3] = np.nan  # read by the skip alone
     with _engine(name, form) as e:
@@ -178,13 +154,13 @@ def test_inf_in_a_skip_column_is_clipped_by_the_prologue(form, monkeypatch):
     """ea_front: the skip reads the normalised, clipped observation; +inf is the Clip's upper bound."""
     monkeypatch.setenv(SW, "1")
     name, B = "ea_front", 5
-    x = ssm.obs(name, B)
+    x = ps.obs(name, B)
     x[1, 7] = np.inf
     big = x.copy()
     big[1, 7] = 1e30  # clipped to the same bound
     with np.errstate(all="ignore"), warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)
-        want = _ref(name).f64(x)
+        want = ps.ref(name).f64(x)
     assert np.isfinite(want).all()
     with _engine(name, form) as e:
         y, yb = e.run(x), e.run(big)
@@ -198,11 +174,11 @@ def test_inf_in_a_skip_column_is_clipped_by_the_prologue(form, monkeypatch):
 def test_resident_tiled0_bitwise_equals_single_launch(name, monkeypatch):
     monkeypatch.setenv(SW, "1")
     with _engine(name, "launch") as s:
-        single = {B: s.run(ssm.obs(name, B)) for B in (1, 8)}
+        single = {B: s.run(ps.obs(name, B)) for B in (1, 8)}
     monkeypatch.setenv("GO2PI_RES_TILED0", "1")
     with _engine(name, "resident") as r:
         for B in (1, 8):
-            assert np.array_equal(r.run(ssm.obs(name, B)), single[B]), (name, B)
+            assert np.array_equal(r.run(ps.obs(name, B)), single[B]), (name, B)
         _served_by(r, "resident")
 
 
@@ -211,12 +187,12 @@ def test_idle_exit_and_relaunch(monkeypatch):
     from go2_onnx_controller_amd import Engine
     monkeypatch.setenv(SW, "1")
     name = "ea_98"
-    with Engine(_path(name), max_batch=8, resident_ms=4) as e:
+    with Engine(ps.path(name), max_batch=8, resident_ms=4) as e:
         assert e.resident_kernel.startswith(MULTI)
-        assert abs_err(e.run(ssm.obs(name, 5)), _want(name, 5)) <= TOL
+        assert abs_err(e.run(ps.obs(name, 5)), ps.want(name, 5)) <= TOL
         assert e.resident_launches == 1
         time.sleep(0.05)  # past resident_ms: the kernel has left
-        assert abs_err(e.run(ssm.obs(name, 8)), _want(name, 8)) <= TOL
+        assert abs_err(e.run(ps.obs(name, 8)), ps.want(name, 8)) <= TOL
         assert e.resident_launches == 2
 
 
@@ -224,16 +200,16 @@ def test_idle_exit_and_relaunch(monkeypatch):
 def test_python_onnx_actor(monkeypatch):
     from go2_onnx_controller_amd import ONNXActor
     name = "ea_k64"
-    obs, act = np.zeros(ssm.in_dim(name), np.float32), np.zeros(12, np.float32)
+    obs, act = np.zeros(ps.in_dim(name), np.float32), np.zeros(12, np.float32)
     monkeypatch.delenv("GO2PI_RESIDENT_MS", raising=False)
     monkeypatch.delenv(SW, raising=False)
-    assert ONNXActor(_path(name), obs, act)._engine.resident_kernel.startswith("none")  # off unless asked for
+    assert ONNXActor(ps.path(name), obs, act)._engine.resident_kernel.startswith("none")  # off unless asked for
     monkeypatch.setenv(SW, "1")
-    actor = ONNXActor(_path(name), obs, act)
+    actor = ONNXActor(ps.path(name), obs, act)
     assert actor.check_dims()
     assert actor._engine.small_kernel == LATENCY and actor._engine.resident_kernel.startswith(MULTI)
-    x = np.concatenate([ssm.obs(name, 8, k) for k in range(3)])[:20]
-    want = _ref(name).f64(x)
+    x = np.concatenate([ps.obs(name, 8, k) for k in range(3)])[:20]
+    want = ps.ref(name).f64(x)
     for i in range(20):
         obs[:] = x[i]  # the caller writes in place, like populate_buffer
         actor.act()
@@ -248,7 +224,7 @@ def test_cpp_onnx_actor_ticks(resident, tmp_path):
     from test_cpu_boundary import build_controller_shape
     exe = build_controller_shape()
     dump, ticks = tmp_path / "actions.bin", 60
-    r = subprocess.run([exe, _path("ea_98"), "ticks", str(ticks), str(dump)], capture_output=True, text=True,
+    r = subprocess.run([exe, ps.path("ea_98"), "ticks", str(ticks), str(dump)], capture_output=True, text=True,
                        timeout=120, env=dict(os.environ, GO2PI_RESIDENT_MS=resident, GO2PI_SKIP_SMALL="1"))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "check_dims: 1" in r.stdout
@@ -257,7 +233,7 @@ def test_cpp_onnx_actor_ticks(resident, tmp_path):
     for t in range(ticks):
         o[t % 98] += np.float32(0.001)
         seq[t] = o
-    assert abs_err(got, _ref("ea_98").f64(seq)) <= TOL
+    assert abs_err(got, ps.ref("ea_98").f64(seq)) <= TOL
     assert not np.array_equal(got[0], got[1])
 
 
@@ -273,4 +249,4 @@ def test_controller_step_is_refused(monkeypatch):
             obs, act = np.zeros((B, 98), np.float32), np.zeros((B, 12), np.float32)
             with pytest.raises(Go2piError, match="does not serve a policy with observation skip inputs"):
                 e.controller_step(st, obs, act, joy=joy)
-        assert abs_err(e.run(ssm.obs("ea_98", 5)), _want("ea_98", 5)) <= TOL  # the engine still serves run()
+        assert abs_err(e.run(ps.obs("ea_98", 5)), ps.want("ea_98", 5)) <= TOL  # the engine still serves run()

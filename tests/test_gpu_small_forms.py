@@ -16,14 +16,13 @@ instantiation's widest input (24 -> 600 -> 8). The switches are read when an eng
 created, so each is set first.
 """
 import functools
-import tempfile
 
 import numpy as np
 import pytest
 
 import ln_ref
 import ln_small_models as lm
-import skip_small_models as ssm
+import policy_specs as ps
 from conftest import abs_err
 
 pytestmark = pytest.mark.gpu
@@ -48,7 +47,7 @@ def _model(name):
     if name == "ln_mixed":
         return synth.ensure_model(name)
     if name == "ea_round2":
-        return ssm.model_path(name, tempfile.mkdtemp(prefix="small_forms_"))
+        return ps.path(name)
     return synth.mlp_model_bytes(**lm.PLAIN_WIDE)
 
 
@@ -58,7 +57,7 @@ def _case(name, B):
     if name == "ln_mixed":
         x = lm.obs(name, B, lm.bitwise_seed(name, B))
     elif name == "ea_round2":
-        x = ssm.obs(name, B, 2)
+        x = ps.obs(name, B, 2)
     else:
         x = lm.plain_wide_obs(B)
     y = ln_ref.LnRef(_model(name)).f64(x)

@@ -88,10 +88,8 @@ def corpus():
     import graphs
     import ln_batched_models
     import ln_small_models
+    import policy_specs as ps
     import probe_models as pm
-    import res_models
-    import skip_models
-    import skip_small_models
     import test_cpu_fuzz
     import test_cpu_layernorm
     import test_cpu_res
@@ -102,8 +100,11 @@ def corpus():
     out += [(f"synth/{n}", make()) for n, make in synth.MODELS.items()]
     out += [(f"graphs/{k}/{seed}", graphs.variant_bytes(k, seed)) for k in graphs.VARIANTS for seed in (0, 3)]
     out += [(f"graphs/{k}", graphs.wide_bytes(k)) for k in graphs.WIDE_VARIANTS + graphs.WIDE_EDGES]
-    for mod in (skip_models, skip_small_models, res_models):
-        out += [(f"{mod.__name__}/{n}", mod.model_bytes(n)) for n in tuple(mod.NAMES) + tuple(mod.PROBES)]
+    # (labelled as before tests/policy_specs.py held these models, so that kept outputs compare)
+    for label, names in (("skip_models", ps.SKIP.names + ps.SKIP.probes),
+                         ("skip_small_models", ps.SMALL_NAMES + ps.SMALL_PROBES),
+                         ("res_models", ps.RES.names + ps.RES.probes)):
+        out += [(f"{label}/{n}", ps.model_bytes(n)) for n in names]
     for mod in (ln_small_models, ln_batched_models):
         out += [(f"{mod.__name__}/{n}", mod.model_bytes(n)) for n in mod.ALL_MODELS]
         out.append((f"{mod.__name__}/zero_variance", mod.zero_variance_model()[0]))
@@ -124,7 +125,7 @@ def corpus():
     test_cpu_fuzz._collect(sink=cases)
     assert len(cases) >= 2000, len(cases)
     out += [(f"fuzz/{i}", d) for i, d in enumerate(cases)]
-    for n in skip_models.NAMES:
+    for n in ps.SKIP.names:
         out += [(f"skip_mut/{n}/{i}", d) for i, d in enumerate(test_cpu_skip._mutations(n, 300))]
     return out, range(first, len(out))
 

@@ -5,7 +5,7 @@ path ("small-batch forms").
 Host to host around one go2pi_run (Engine.run_ptr on fixed buffers, the observation rewritten
 before every call), p50 / p99 over `--calls` calls after `--warmup`, on ea_k64 (270 -> 128 ->
 64 -> 19, [obs[0:45] | z] -> 512 -> 256 -> 128 -> 12: seven layers) and ea_98 (six layers) of
-tests/skip_models.py. Legs:
+tests/policy_specs.py. Legs:
   a         GO2PI_SKIP_SMALL unset: gemv_layer_kernel, one launch per layer replayed as a graph
   a_parent  the same on another build of the library (--parent-lib: the parent commit's), control
   b         GO2PI_SKIP_SMALL=1, resident_ms = 0: policy_latency_kernel, one launch
@@ -47,7 +47,7 @@ def child(args):
     import tempfile
 
     import numpy as np
-    import skip_models as sm
+    import policy_specs as ps
     from go2_onnx_controller_amd import Engine, synth
 
     leg, out = args.leg, {}
@@ -70,7 +70,7 @@ def child(args):
                 with open(p, "wb") as fh:
                     fh.write(synth.mlp_model_bytes(dims=PLAIN[name], seed=61, act="Elu"))
             else:
-                p = sm.model_path(name, d)
+                p = ps.model_path(name, d)
             models[name] = (p, {}, ())
         res_ms = args.resident_ms if leg in ("c", "d") else 0
     for name, (path, kw, switches) in models.items():
