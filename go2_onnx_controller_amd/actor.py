@@ -40,7 +40,8 @@ class ONNXActor:
         # as the C++ shim: a resident kernel serves act() (no launch per tick), leaving
         # after 100 ms without one; GO2PI_RESIDENT_MS=0 -> one launch per call
         engine_kwargs.setdefault("resident_ms", int(os.environ.get("GO2PI_RESIDENT_MS", "100")))
-        # (GO2PI_SKIP_SMALL, for a policy with observation skip inputs, is read by the engine itself)
+        # (GO2PI_SKIP_SMALL, for a policy with observation skip inputs, and GO2PI_RESIDUAL_SMALL, for one with
+        # residual connections, are read by the engine itself)
         # GO2PI_LN_SMALL=1: a LayerNormalization policy's act() takes the single-launch and
         # resident kernels too (Engine(ln_small=True)); off otherwise
         engine_kwargs.setdefault("ln_small", os.environ.get("GO2PI_LN_SMALL", "0") == "1")

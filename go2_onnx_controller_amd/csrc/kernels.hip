@@ -174,8 +174,18 @@ __device__ __forceinline__ bool sweep_layer(unsigned long long *gran, int n, uns
 // front of the sweep, and only their LDS stores stand behind its barrier. A layer-0 gather
 // stages its columns through the index table.
 constexpr int LAT_SKIPV = 4;
-
-template <bool CTL, bool LNORM = false, bool SKIP = false>
+// RES (with LNORM and SKIP; act() only): the instantiation of a program with residual
+// connections (DevProgram::res; GO2PI_RESIDUAL_SMALL). Workgroup g owns tile g of every layer
+// and a consumer has its source's width, so the carried value of column 16 g + lane, row b, is
+// computed at the source layer by the publishing lane that adds it at the consumer layer: it
+// stays in that lane's registers (carried[b]) and never leaves the workgroup. No granule, tag,
+// sweep or barrier is added. A consumer's value is act((sum + bias) + carried), tile_finish's
+// order; a source keeps the value it publishes (a pre-LN layer's raw sum: the consumer's staging
+// normalises the granules, never the carried value), behind the consumer's read where a layer is
+// both. carried[] starts at zero and a consumer clears what it read, so a workgroup that owns no
+// tile of the source (a consumer padded wider than its source) adds 0, and one that owns no tile
+// of a layer between source and consumer (a bottleneck) keeps the value across it.
+template <bool CTL, bool LNORM = false, bool SKIP = false, bool RES = false>
 __device__ __forceinline__ void latency_body(const DevProgram &P, const float *obs, float *act, int B,
                                              unsigned epoch0, unsigned long long *gran, int gstride, unsigned *err,
                                              unsigned *done, const DevCtl ctl) {
@@ -197,6 +207,14 @@ __device__ __forceinline__ void latency_body(const DevProgram &P, const float *o
       ctl_lds_load(CL, ctl, 0, B, P.in_dim, tid, wave, lane, LAT_WAVES);
       lds_dma_wait();  // (the assembly reads the image after this workgroup's next barrier)
     }
+  }
+  // RES: the consumer and source layers, read once (as fused_body reads consm / srcm), and the
+  // publishing lanes' carried rows
+  const ResMasks rm = RES ? res_masks(P) : ResMasks{0u, 0u};
+  float carried[GO2PI_SMALL_MAXB];
+  if constexpr (RES) {
+#pragma unroll
+    for (int b = 0; b < GO2PI_SMALL_MAXB; ++b) carried[b] = 0.f;
   }
   for (int l = 0; l < P.nl; ++l) {
     const DevLayer &L = P.L[l];
@@ -343,6 +361,34 @@ __device__ __forceinline__ void latency_body(const DevProgram &P, const float *o
       const int la = L.act, LN = L.N;  // (read once: the stores below would make each row reload them)
       const float lal = L.alpha, lbe = L.beta;
       const Post po = post_of(P);
+      if constexpr (RES) {
+        // The residual instantiation's own text of the loop below (act() only), unrolled over the
+        // eight rows: carried[] indexed by a run-time b would live in scratch.
+        const bool cons = (rm.cons >> l) & 1u, src = (rm.src >> l) & 1u;  // uniform
+#pragma unroll
+        for (int b = 0; b < GO2PI_SMALL_MAXB; ++b) {
+          if (b < B) {
+            float s = 0.f;
+            for (int w2 = 0; w2 < LAT_WAVES; ++w2) s += part[(w2 * GO2PI_SMALL_MAXB + b) * 16 + lane];
+            float sb = s + bv;
+            if (cons) sb += carried[b], carried[b] = 0.f;  // (sum + bias) + carried; read once
+            const float v = act_fn(la, lal, lbe, sb);
+            if (src) carried[b] = v;  // behind the read: a layer may be both
+            if (last) {
+              if (n < LN) act[(size_t)b * LN + n] = post_fn(po, v);
+              if (done && b == B - 1 && g == 0) {  // the completion word, as below
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (lane == 0 && T == 1) __hip_atomic_store(done, epoch0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+              }
+            } else {
+              const unsigned long long gv = ((unsigned long long)(epoch0 + (unsigned)l) << 32) | __float_as_uint(v);
+              __hip_atomic_store(gran + (size_t)l * gstride + b * L.N_pad + n, gv, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+            }
+          }
+        }
+      } else {
       for (int b = 0; b < B; ++b) {
         float s = 0.f;
         for (int w2 = 0; w2 < LAT_WAVES; ++w2) s += part[(w2 * GO2PI_SMALL_MAXB + b) * 16 + lane];
@@ -365,6 +411,7 @@ __device__ __forceinline__ void latency_body(const DevProgram &P, const float *o
                              __HIP_MEMORY_SCOPE_AGENT);
         }
       }
+      }  // (the loop every other instantiation runs keeps its text and indentation)
     }
     lds_barrier();  // xs / part reused by the next layer (the granule stores stay in flight)
   }
@@ -419,6 +466,15 @@ __global__ __launch_bounds__(LAT_WAVES * 64) void policy_latency_skip_kernel(con
   latency_body<false, true, true>(*Pd, obs, act, B, epoch0, gran, gstride, err, done, DevCtl{});
 }
 
+// ... and the instantiation of a program with residual connections (the skip code too: a
+// policy may have both, and the skip paths are uniform branches on skip_n)
+__global__ __launch_bounds__(LAT_WAVES * 64) void policy_latency_res_kernel(const DevProgram *__restrict__ Pd,
+                                                                            const float *obs, float *act, int B,
+                                                                            unsigned epoch0, unsigned long long *gran,
+                                                                            int gstride, unsigned *err, unsigned *done) {
+  latency_body<false, true, true, true>(*Pd, obs, act, B, epoch0, gran, gstride, err, done, DevCtl{});
+}
+
 int latency_grid(const DevProgram &p) {
   int grid = 1;
   for (int l = 0; l < p.nl; ++l) grid = std::max(grid, p.L[l].N_pad >> 4);
@@ -436,7 +492,8 @@ int launch_latency(const DevProgram &p, const DevProgram *p_dev, const float *ob
   if (batch > GO2PI_SMALL_MAXB) return (int)hipErrorInvalidValue;
   const int grid = latency_grid(p);
   const size_t lds = sizeof(float) * latency_lds_of(p, false).total;
-  hipLaunchKernelGGL(program_has_skip(p)        ? policy_latency_skip_kernel
+  hipLaunchKernelGGL(program_has_res(p)         ? policy_latency_res_kernel
+                     : program_has_skip(p)      ? policy_latency_skip_kernel
                      : program_small_general(p) ? policy_latency_ln_kernel
                                                 : policy_latency_kernel,
                      dim3(grid), dim3(LAT_WAVES * 64), lds, reinterpret_cast<hipStream_t>(stream), p_dev, obs, act, batch,
@@ -448,7 +505,9 @@ int launch_latency_ctl(const DevProgram &p, const DevProgram *p_dev, const DevCt
                        unsigned long long *gran, int gstride, unsigned *err, unsigned *done, void *stream) {
   if (batch <= 0) return 0;
   // (no controller form reads a skip layer's observation columns: the engine refuses the tick)
-  if (batch > GO2PI_SMALL_MAXB || p.L[p.nl - 1].N_pad != 16 || program_has_skip(p)) return (int)hipErrorInvalidValue;
+  // (nor has one a carried value)
+  if (batch > GO2PI_SMALL_MAXB || p.L[p.nl - 1].N_pad != 16 || program_has_skip(p) || program_has_res(p))
+    return (int)hipErrorInvalidValue;
   const int grid = latency_grid(p);
   const size_t lds = sizeof(float) * latency_lds_of(p, true).total;
   hipLaunchKernelGGL(program_small_general(p) ? policy_latency_ctl_ln_kernel : policy_latency_ctl_kernel, dim3(grid),

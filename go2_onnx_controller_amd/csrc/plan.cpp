@@ -213,6 +213,11 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   // small_batch; nothing else. Only the 8-wave instantiation is built (a general-body unit
   // takes minutes to compile), so an explicit waves = 4 or 16 is refused, and the
   // GO2PI_LN_BATCHED, ln_small and GO2PI_SKIP_SMALL bits have no effect on such a program.
+  // With GO2PI_RESIDUAL_SMALL (Switches::residual_small) the single launch serves it at batch
+  // <= 8 and, of the resident forms, the multi-workgroup kernel's act() with a tiled layer 0
+  // (plan_resident; resident.hip multi_nf), under the shape conditions of any dense program;
+  // an LN + residual program needs the GO2PI_LN_SMALL bit beside it, a skip + residual
+  // program GO2PI_SKIP_SMALL.
   pl.has_res = program_has_res(p);
   if (pl.has_res && (o.waves == 4 || o.waves == 16))
     throw ApiError("a policy with residual connections runs on the 8-wave batched kernel only: waves = " +
@@ -370,8 +375,9 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   // (a LayerNormalization policy: only with opts.ln_small's GO2PI_LN_SMALL bit, ln_bits;
   // latency_body normalises the swept rows as gemv_layer_kernel does)
   // (a policy with observation skip inputs: only with GO2PI_SKIP_SMALL)
+  // (a policy with residual connections: only with GO2PI_RESIDUAL_SMALL)
   pl.latency_ok = !m.has_gru && pl.latency_shape && (!pl.has_ln || (ln_bits(o) & GO2PI_LN_SMALL)) &&
-                  (!pl.has_skip || sw.skip_small) && !pl.has_res;
+                  (!pl.has_skip || sw.skip_small) && (!pl.has_res || sw.residual_small);
   // the resident kernel's GRU / LSTM form (resident.hip, RNN): the cell tiled in front
   // of the dense layers, h' carried between requests as granules (an LSTM's c in the
   // owning workgroups' LDS)
@@ -461,11 +467,13 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
 // A policy with observation skip inputs (GO2PI_SKIP_SMALL): the multi-workgroup kernel's
 // act() and nothing else: the single-workgroup and wide forms keep a layer's input in
 // registers or in layouts with no room for the skip columns, and the tick is refused.
+// A policy with residual connections (GO2PI_RESIDUAL_SMALL): the same, for the carried value:
+// only the multi-workgroup kernel's publishing lanes hold one across layers.
 ResForms plan_resident(const Plan &pl, const Switches &sw, bool resident_ok, bool ring_in_vram) {
   ResForms r;
   if (!resident_ok) return r;
   const DevProgram &p = pl.prog;
-  if (pl.has_skip) {
+  if (pl.has_skip || pl.has_res) {
     r.act = ResForm::Multi;
     return r;
   }

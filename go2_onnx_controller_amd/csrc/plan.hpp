@@ -45,6 +45,9 @@ struct Switches {
   // SKIP_SMALL (opt-in, not a diagnostic): a policy with observation skip inputs at batch <= 8 by the
   // single launch and the multi-workgroup resident kernel, not the GEMV chain
   bool skip_small;
+  // RESIDUAL_SMALL (opt-in, not a diagnostic; RES_* means "resident" here): a policy with residual connections
+  // at batch <= 8 by the single launch and the multi-workgroup resident kernel, not the GEMV chain
+  bool residual_small;
 
   static Switches read() {
     auto env = [](const char *name) { return std::getenv(name); };  // (the engine's only look at the environment)
@@ -59,7 +62,8 @@ struct Switches {
                     .gru_general = on("GO2PI_GRU_GENERAL"), .ctl_general = on("GO2PI_CTL_GENERAL"),
                     .res_multi = on("GO2PI_RES_MULTI"), .res_r1w = on("GO2PI_RES_R1W"),
                     .res_tiled0 = on("GO2PI_RES_TILED0"), .a1_depth = num("GO2PI_A1_DEPTH") == 1 ? 1 : 2,
-                    .a1_cw = num("GO2PI_A1_CW") == 4 ? 4 : 8, .skip_small = on("GO2PI_SKIP_SMALL")};
+                    .a1_cw = num("GO2PI_A1_CW") == 4 ? 4 : 8, .skip_small = on("GO2PI_SKIP_SMALL"),
+                    .residual_small = on("GO2PI_RESIDUAL_SMALL")};
   }
 };
 
@@ -90,7 +94,9 @@ struct Plan {
   bool one_round = false;      // every layer past the first has K_pad <= 512: one sweep round
   bool has_ln = false;         // a LayerNormalization on any layer
   bool has_skip = false;       // an observation skip input on any layer (small-batch kernels: Switches::skip_small)
-  bool has_res = false;        // a residual connection on any layer (policy_fused_res_kernel<8> and the GEMV chain)
+  // a residual connection on any layer (policy_fused_res_kernel<8> and the GEMV chain; small-batch kernels:
+  // Switches::residual_small)
+  bool has_res = false;
   go2pi_cost cost{};
   // whether build() sets up the resident path (the request ring and its kernel)
   bool resident(const go2pi_opts &o) const { return (latency_ok || res_rnn) && done_ok && o.resident_ms > 0; }

@@ -184,7 +184,8 @@ struct DevProgram {
   const int *skip_idx[GO2PI_MAX_LAYERS];
   // Residual connections (onnx_model.hpp Dense::res): res[l] = j + 1 where layer j's carried
   // value is added to layer l's Gemm (+ bias) output in front of its activation / LN, 0: none
-  // (so a zeroed program has none). Served by policy_fused_res_kernel and the GEMV chain.
+  // (so a zeroed program has none). Served by policy_fused_res_kernel and the GEMV chain, and
+  // by policy_latency_res_kernel / policy_resident_kernel<.., RES> (GO2PI_RESIDUAL_SMALL).
   int res[GO2PI_MAX_LAYERS];
 };
 
@@ -220,7 +221,8 @@ inline bool program_has_skip(const DevProgram &p) {
 }
 
 // a residual connection on any layer: served by the general batched body's residual
-// instantiation (policy_fused_res_kernel<8>) and the GEMV chain only (plan.cpp plan_program)
+// instantiation (policy_fused_res_kernel<8>) and the GEMV chain, and with GO2PI_RESIDUAL_SMALL
+// by the small-batch kernels' residual instantiations (plan.cpp plan_program)
 inline bool program_has_res(const DevProgram &p) {
   for (int l = 0; l < p.nl; ++l)
     if (p.res[l]) return true;
@@ -235,10 +237,25 @@ inline bool program_has_res(const DevProgram &p) {
 // observation skip inputs is a general one too; the launchers give it the general
 // instantiation that also fills the skip columns (policy_latency_skip_kernel,
 // policy_resident_kernel<.., true, true>), so the other general programs run the code they ran.
+// A program with residual connections (GO2PI_RESIDUAL_SMALL) likewise: its one instantiation
+// holds the LN pass, the second round, the skip code and the carried value
+// (policy_latency_res_kernel, policy_resident_kernel<0, false, 0, true, true, true>).
 inline bool program_small_general(const DevProgram &p) {
   for (int l = 1; l < p.nl; ++l)
     if (p.L[l].K_pad > 512) return true;
-  return program_has_ln(p) || program_has_skip(p);
+  return program_has_ln(p) || program_has_skip(p) || program_has_res(p);
+}
+
+// The residual layers of a program as two bit masks, read once by a kernel: bit l of cons: layer
+// l adds a carried value; bit j of src: layer j's value is carried to a later layer.
+struct ResMasks {
+  unsigned cons, src;
+};
+constexpr ResMasks res_masks(const DevProgram &p) {  // (constexpr: callable from device code too)
+  ResMasks m{0u, 0u};
+  for (int l = 0; l < p.nl; ++l)
+    if (p.res[l]) m.cons |= 1u << l, m.src |= 1u << (p.res[l] - 1);
+  return m;
 }
 
 // ---------------------------------------------------------------------------

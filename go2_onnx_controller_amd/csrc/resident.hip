@@ -308,7 +308,17 @@ __device__ __forceinline__ void skip_fill(const DevProgram &P, int l, const int 
 // the barrier that ends that path. A thread's first RES_SKIPV indices are loaded in front of
 // the sweep. No granule, tag or wait between workgroups is added. A layer-0 gather runs the
 // tiled layer 0 (launch_resident: multi_nf), staged through the index table.
-template <int NF, bool CTL, int RNN = 0, bool LNORM = false, bool SKIP = false>
+// RES (with SKIP, NF = 0): the instantiation of a program with residual connections
+// (DevProgram::res; GO2PI_RESIDUAL_SMALL), policy_latency_res_kernel's arithmetic in the same
+// place: workgroup g owns tile g of every layer (layer 0 tiled: with a local layer 0 no
+// publishing lane would own the source's columns), so a publishing lane adds at the consumer
+// layer the value it computed itself at the source layer, held in its registers (carried[b]).
+// No granule, tag, wait, spin or barrier is added. The kernel serves many requests: carried[]
+// is cleared once, in front of the request loop; a consumer clears what it read, and the source
+// layer of each request rewrites every element its consumer reads, so a lane of a workgroup
+// that owns no tile of the source adds 0 for the kernel's life. Rows b >= B of an earlier,
+// larger request are stale and never read; a request abandoned on a LEAVE tag ends the launch.
+template <int NF, bool CTL, int RNN = 0, bool LNORM = false, bool SKIP = false, bool RES = false>
 __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const DevProgram *__restrict__ Pd,
                                                                          const u64 *req, u64 *actg, u64 *gran,
                                                                          int gstride, u64 *mirror, unsigned *err,
@@ -318,6 +328,7 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
   static_assert(!(RNN && (NF > 0 || CTL)), "the GRU form tiles layer 0 and serves act() only");
   static_assert(!(LNORM && (CTL || RNN)), "LayerNormalization: the dense act() form only");
   static_assert(!SKIP || LNORM, "skip inputs: the general instantiation only");
+  static_assert(!RES || (SKIP && NF == 0), "residual connections: the skip instantiation with a tiled layer 0 only");
   constexpr bool LOCAL0 = NF > 0;
   constexpr bool LSTM = RNN == 2;
   constexpr int NG = LSTM ? 4 : 3;  // gate fragments per (chunk, tile)
@@ -418,6 +429,13 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
   // compiler's waitcnt pass knows it: no vmcnt(0) in front of their first uses,
   // which would also wait for the stores a request has in flight by then)
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+  // RES: the consumer and source layers, read once, and the publishing lanes' carried rows
+  const ResMasks rm = RES ? res_masks(P) : ResMasks{0u, 0u};
+  float carried[GO2PI_SMALL_MAXB];
+  if constexpr (RES) {
+#pragma unroll
+    for (int b = 0; b < GO2PI_SMALL_MAXB; ++b) carried[b] = 0.f;
+  }
 
   for (;;) {
     // ---- wait for a request. Workgroup 0 polls the host (header + the first
@@ -762,6 +780,31 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
         const int la = L.act, LN = L.N, LNP = L.N_pad;  // (read once: the stores below would make each row reload them)
         const float lal = L.alpha, lbe = L.beta;
         const Post po = post_of(P);
+        if constexpr (RES) {
+          // The residual instantiation's own text of the loop below (act() only), unrolled over
+          // the eight rows: carried[] indexed by a run-time b would live in scratch.
+          const bool cons = (rm.cons >> l) & 1u, src = (rm.src >> l) & 1u;  // uniform
+#pragma unroll
+          for (int b = 0; b < GO2PI_SMALL_MAXB; ++b) {
+            if (b < B) {
+              float s = 0.f;
+              for (int w2 = 0; w2 < RES_WAVES; ++w2) s += part[(w2 * GO2PI_SMALL_MAXB + b) * 16 + lane];
+              float sb = s + bcur;
+              if (cons) sb += carried[b], carried[b] = 0.f;  // (sum + bias) + carried; read once
+              const float v = act_fn(la, lal, lbe, sb);
+              if (src) carried[b] = v;  // behind the read: a layer may be both
+              if (lastl) {
+                if (n < LN)
+                  __hip_atomic_store(actg + (size_t)b * LN + n, ((u64)e << 32) | __float_as_uint(post_fn(po, v)),
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+              } else {
+                const u64 gv = ((u64)(e + 1u + (unsigned)l) << 32) | __float_as_uint(v);
+                __hip_atomic_store(gran + (size_t)l * gstride + b * LNP + n, gv, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+              }
+            }
+          }
+        } else {
         for (int b = 0; b < B; ++b) {
           float s = 0.f;
           for (int w2 = 0; w2 < RES_WAVES; ++w2) s += part[(w2 * GO2PI_SMALL_MAXB + b) * 16 + lane];
@@ -781,6 +824,7 @@ __global__ __launch_bounds__(RES_WAVES * 64) void policy_resident_kernel(const D
                                __HIP_MEMORY_SCOPE_AGENT);
           }
         }
+        }  // (the loop every other instantiation runs keeps its text and indentation)
       }
       if (l == 1) RES_STAMP(14);  // layer 1: wave 0's granules stored
       lds_barrier();  // xs / part reused by the next layer
@@ -1803,9 +1847,15 @@ int launch_resident1(const DevProgram &p, const DevProgram *p_dev, const unsigne
 // local layer 0 where each thread's share of it fits NF = 8, 12 or 16 registers' fragments:
 // that NF, else 0 (layer 0 tiled)
 // (a layer-0 gather, DevLayer::skip_n on layer 0: tiled, its staging loop gathers)
+// (a program with residual connections: tiled. With a local layer 0 every workgroup computes all
+// of layer 0 and no publishing lane owns its columns, and layer 0 is the source in SimBa and in
+// ResNet-v1 alike)
 static int multi_nf(const DevProgram &p, bool tiled0) {
   const int nf = local0_geometry(p.L[0].K_pad, p.L[0].N_pad).nf;
-  return (!p.has_gru && p.nl >= 2 && (nf == 8 || nf == 12 || nf == 16) && !tiled0 && !p.L[0].skip_n) ? nf : 0;
+  return (!p.has_gru && p.nl >= 2 && (nf == 8 || nf == 12 || nf == 16) && !tiled0 && !p.L[0].skip_n &&
+          !program_has_res(p))
+             ? nf
+             : 0;
 }
 
 MultiLds multi_lds_of(const DevProgram &p, bool ctl, bool tiled0) {
@@ -1840,6 +1890,8 @@ int launch_resident(const DevProgram &p, const DevProgram *p_dev, const unsigned
   // (engine.cpp selects neither the controller nor the recurrent form for those)
   const bool gen = program_small_general(p);
   if (gen && (ctl || rnn)) return (int)hipErrorInvalidValue;
+  // residual connections: one instantiation, layer 0 tiled (multi_nf), the skip code in it
+  if (program_has_res(p)) return go(policy_resident_kernel<0, false, 0, true, true, true>);
   if (program_has_skip(p)) {  // (a general program: program_small_general)
     if (local0 && nf == 8) return go(policy_resident_kernel<8, false, 0, true, true>);
     if (local0 && nf == 12) return go(policy_resident_kernel<12, false, 0, true, true>);

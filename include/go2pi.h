@@ -126,10 +126,16 @@ void go2pi_default_opts(go2pi_opts *opts);
    LayerNormalization's output, a held constant Mul / Div on the source, and any residual
    connection beside a GRU or LSTM cell. Such a policy is served by
    policy_fused_res_kernel<8> and, at batch <= small_batch, by one launch per layer
-   (replayed as a graph); opts.waves = 4 or 16 fails with GO2PI_E_INVALID for it, it has no
-   single-launch or resident kernel (resident_ms is accepted and go2pi_resident_kernel
-   reports "none"; ln_small and GO2PI_SKIP_SMALL have no effect on it), and
-   go2pi_controller_step* returns GO2PI_E_INVALID. go2pi_inspect_model reports each layer's
+   (replayed as a graph); opts.waves = 4 or 16 fails with GO2PI_E_INVALID for it, by default
+   it has no single-launch or resident kernel (resident_ms is accepted and
+   go2pi_resident_kernel reports "none"; ln_small and GO2PI_SKIP_SMALL have no effect on it),
+   and go2pi_controller_step* returns GO2PI_E_INVALID, switch or not. With
+   GO2PI_RESIDUAL_SMALL set in the environment when the engine is created (to any value; it
+   holds for the engine's life) a policy of the single launch's shape is served at batch <=
+   small_batch by policy_latency_kernel and, with resident_ms > 0, by the multi-workgroup
+   policy_resident_kernel (never by a single-workgroup or the wide resident kernel); a
+   policy that also has a LayerNormalization (every SimBa model) needs ln_small's bit 1 as
+   well, one that also has a skip input GO2PI_SKIP_SMALL. go2pi_inspect_model reports each layer's
    "res": the index of the layer whose carried value it adds, or -1.
    LayerNormalization (opset 17, over the feature axis, epsilon from the attribute, Scale
    and optional B constant, only output 0 used) is accepted on any dense layer but the last,
