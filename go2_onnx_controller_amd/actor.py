@@ -41,7 +41,8 @@ class ONNXActor:
         # after 100 ms without one; GO2PI_RESIDENT_MS=0 -> one launch per call
         engine_kwargs.setdefault("resident_ms", int(os.environ.get("GO2PI_RESIDENT_MS", "100")))
         # (GO2PI_SKIP_SMALL, for a policy with observation skip inputs, and GO2PI_RESIDUAL_SMALL, for one with
-        # residual connections, are read by the engine itself)
+        # residual connections, are read by the engine itself; so is GO2PI_RESIDUAL_BATCHED, which moves such a
+        # policy's batched launches alone and leaves act() as it is)
         # GO2PI_LN_SMALL=1: a LayerNormalization policy's act() takes the single-launch and
         # resident kernels too (Engine(ln_small=True)); off otherwise
         engine_kwargs.setdefault("ln_small", os.environ.get("GO2PI_LN_SMALL", "0") == "1")

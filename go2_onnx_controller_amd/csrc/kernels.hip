@@ -559,11 +559,18 @@ static int with_w4ln(const DevProgram &p, F &&f) {
   }
 }
 
+// a residual program on the pipeline (kernels_w4res_t{2,4,8}.hip; GO2PI_RESIDUAL_BATCHED): the LN
+// pipeline's fields, policy_mlp_res_kernel
+static bool w4res_program(const DevProgram &p) { return p.w4ln_tpw != 0 && program_has_res(p); }
+
 int configure_kernels(const DevProgram &p, int waves) {
   hipError_t e = hipSuccess;
   // (an LN pipeline program: its batched kernel, and the general body too, which serves its
-  // controller tick)
-  if (p.w4ln_tpw) {
+  // controller tick; a residual pipeline program: likewise, the general residual kernel beside it)
+  if (w4res_program(p)) {
+    e = (hipError_t)with_w4ln(p, [&](auto t) { return w4res_configure<decltype(t)::value>(p); });
+    if (e != hipSuccess) return (int)e;
+  } else if (p.w4ln_tpw) {
     e = (hipError_t)with_w4ln(p, [&](auto t) { return w4ln_configure<decltype(t)::value>(p); });
     if (e != hipSuccess) return (int)e;
   }
@@ -584,6 +591,10 @@ int configure_kernels(const DevProgram &p, int waves) {
 int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves, const float *obs, float *act,
                         float *hidden, int batch, int steps, void *stream) {
   if (batch <= 0 || steps <= 0) return 0;
+  if (w4res_program(p))
+    return with_w4ln(p, [&](auto t) {
+      return w4res_launch<decltype(t)::value>(p, p_dev, obs, act, batch, steps, stream);
+    });
   if (program_has_res(p)) return waves == 8 ? res_launch(p, p_dev, obs, act, batch, steps, stream) : (int)hipErrorInvalidValue;
   if (p.w4ln_tpw)
     return with_w4ln(p, [&](auto t) {
@@ -599,6 +610,7 @@ int launch_policy_fused(const DevProgram &p, const DevProgram *p_dev, int waves,
 }
 
 int batched_kernel_name(const DevProgram &p, int waves, char *buf, size_t cap) {
+  if (w4res_program(p)) return with_w4ln(p, [&](auto t) { return w4res_name<decltype(t)::value>(p, buf, cap); });
   if (program_has_res(p)) return res_name(p, buf, cap);
   if (p.w4ln_tpw) return with_w4ln(p, [&](auto t) { return w4ln_name<decltype(t)::value>(p, buf, cap); });
   if (waves == 4 && p.w4_tpw) return with_w4(p, [&](auto t) { return w4_name<decltype(t)::value>(p, buf, cap); });

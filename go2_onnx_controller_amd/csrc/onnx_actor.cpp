@@ -60,7 +60,8 @@ ONNXActor::ONNXActor(const std::string &model_path, const std::span<float> obser
   opts.resident_ms = 100;
   if (const char *v = std::getenv("GO2PI_RESIDENT_MS")) opts.resident_ms = std::atoi(v);
   // (GO2PI_SKIP_SMALL, for a policy with observation skip inputs, and GO2PI_RESIDUAL_SMALL, for one with
-  // residual connections, are read by the engine itself)
+  // residual connections, are read by the engine itself; so is GO2PI_RESIDUAL_BATCHED, which moves such a policy's
+  // batched launches alone and leaves act() as it is)
   // GO2PI_LN_SMALL=1: a LayerNormalization policy's act() takes the single-launch and
   // resident kernels too (go2pi_opts.ln_small; off otherwise: one launch per layer)
   if (const char *v = std::getenv("GO2PI_LN_SMALL")) opts.ln_small = std::atoi(v) == 1 ? 1 : 0;

@@ -65,15 +65,17 @@ void pack_gru(const Gru &g, std::vector<float> &w, int &I_pad) {
 }
 
 // The pipeline's shape test (w4_eligible below; the LN pipeline, plan_program): the tiles per
-// wave (2, 4 or 8) of a policy whose dense layers it serves, else 0.
-int w4_shape_tpw(const Model &m) {
+// wave (2, 4 or 8) of a policy whose dense layers it serves, else 0. uniform_act = false: the
+// hidden layers need not share an activation (the residual pipeline reads each layer's own).
+int w4_shape_tpw(const Model &m, bool uniform_act = true) {
   const int nl = (int)m.layers.size();
   if (nl < 2) return 0;
   const int tpw = ceil64(m.layers[0].N) / 64, t_last = ceil16(m.layers[nl - 1].N) / 16;
   if (!(tpw == 2 || tpw == 4 || tpw == 8) || t_last > (tpw == 8 ? 1 : 2)) return 0;
   for (int l = 0; l + 1 < nl; ++l)
-    if (ceil64(m.layers[l].N) != 64 * tpw || m.layers[l].act != m.layers[0].act ||
-        m.layers[l].alpha != m.layers[0].alpha || m.layers[l].beta != m.layers[0].beta)
+    if (ceil64(m.layers[l].N) != 64 * tpw ||
+        (uniform_act && (m.layers[l].act != m.layers[0].act || m.layers[l].alpha != m.layers[0].alpha ||
+                         m.layers[l].beta != m.layers[0].beta)))
       return 0;
   return tpw;
 }
@@ -213,6 +215,9 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   // small_batch; nothing else. Only the 8-wave instantiation is built (a general-body unit
   // takes minutes to compile), so an explicit waves = 4 or 16 is refused, and the
   // GO2PI_LN_BATCHED, ln_small and GO2PI_SKIP_SMALL bits have no effect on such a program.
+  // With GO2PI_RESIDUAL_BATCHED (Switches::residual_batched) a program of the pipeline's shape
+  // runs its batched launches on policy_mlp_res_kernel (below, w4ln_tpw); waves = 4 / 16 stay
+  // refused, and every other launch of the engine runs what it runs without the switch.
   // With GO2PI_RESIDUAL_SMALL (Switches::residual_small) the single launch serves it at batch
   // <= 8 and, of the resident forms, the multi-workgroup kernel's act() with a tiled layer 0
   // (plan_resident; resident.hip multi_nf), under the shape conditions of any dense program;
@@ -396,9 +401,17 @@ Plan plan_program(const Model &m, const go2pi_opts &o, const Switches &sw) {
   // observation no wider than the hidden layers). The program stays the general body's in
   // every other respect, so the controller tick, the GEMV chain, the single launch and the
   // resident forms run what they run without the bit. Anything else keeps the general body.
-  if ((ln_bits(o) & GO2PI_LN_BATCHED) && pl.has_ln && !pl.has_skip && !pl.has_res && !m.has_gru && o.waves == 0 &&
-      !sw.no_w4 && !sw.no_head_fuse) {
-    const int tpw = w4_shape_tpw(m), nh = p.nl - 1;
+  // The pipeline's residual kernel (policy_mlp_res_kernel, the same body with the carried value
+  // in registers) with GO2PI_RESIDUAL_BATCHED: a residual program, with or without an LN and
+  // whatever opts.ln_small says, under the same conditions, except that its hidden layers need
+  // not share an activation. It takes the LN pipeline's fields (w4ln_tpw, the pack: zero Scale
+  // / B for a layer without LN); w4ln_tpw != 0 && program_has_res(p) identifies the form.
+  // Anything else (a skip input, 64-wide or non-uniform hidden layers, waves = 8, a prologue)
+  // keeps policy_fused_res_kernel<8>.
+  const bool ln_pipe = (ln_bits(o) & GO2PI_LN_BATCHED) && pl.has_ln && !pl.has_res;
+  const bool res_pipe = sw.residual_batched && pl.has_res;
+  if ((ln_pipe || res_pipe) && !pl.has_skip && !m.has_gru && o.waves == 0 && !sw.no_w4 && !sw.no_head_fuse) {
+    const int tpw = w4_shape_tpw(m, !res_pipe), nh = p.nl - 1;
     const bool bare = buf.pre_sub.empty() && buf.pre_div.empty() && buf.pre_mul.empty() && !p.pre_clip &&
                       post_plain(p) && p.lds_stride == 64 * tpw + 4;
     if (tpw && bare && p.in_dim < 4096 && p.L[0].K_pad / 16 < 256 && (p.L[0].K_pad / 16) % 4 == 0 &&

@@ -48,6 +48,10 @@ struct Switches {
   // RESIDUAL_SMALL (opt-in, not a diagnostic; RES_* means "resident" here): a policy with residual connections
   // at batch <= 8 by the single launch and the multi-workgroup resident kernel, not the GEMV chain
   bool residual_small;
+  // RESIDUAL_BATCHED (opt-in, not a diagnostic): a policy with residual connections of the 4-wave
+  // pipeline's shape on policy_mlp_res_kernel for batched launches, not policy_fused_res_kernel<8>
+  // (plan.cpp plan_program). An environment switch for RESIDUAL_SMALL's reason: go2pi_opts ends in ln_small
+  bool residual_batched;
 
   static Switches read() {
     auto env = [](const char *name) { return std::getenv(name); };  // (the engine's only look at the environment)
@@ -63,7 +67,8 @@ struct Switches {
                     .res_multi = on("GO2PI_RES_MULTI"), .res_r1w = on("GO2PI_RES_R1W"),
                     .res_tiled0 = on("GO2PI_RES_TILED0"), .a1_depth = num("GO2PI_A1_DEPTH") == 1 ? 1 : 2,
                     .a1_cw = num("GO2PI_A1_CW") == 4 ? 4 : 8, .skip_small = on("GO2PI_SKIP_SMALL"),
-                    .residual_small = on("GO2PI_RESIDUAL_SMALL")};
+                    .residual_small = on("GO2PI_RESIDUAL_SMALL"),
+                    .residual_batched = on("GO2PI_RESIDUAL_BATCHED")};
   }
 };
 
@@ -74,7 +79,9 @@ struct HostBuffers {
   std::vector<size_t> off;
   std::vector<float> bias[GO2PI_MAX_LAYERS], ln_g[GO2PI_MAX_LAYERS], ln_b[GO2PI_MAX_LAYERS];  // [N_pad] each
   std::vector<float> bpack;      // the pipeline's bias pack (w4_bpack): the hidden layers' biases back to back
-  std::vector<float> lnpack;     // the LN pipeline's pack (program.hpp w4ln_tpw): biases | Scale | B of the hidden layers
+  // the LN pipeline's pack (program.hpp w4ln_tpw): biases | Scale | B of the hidden layers; the residual
+  // pipeline's too (zeros for Scale / B of a layer without LN)
+  std::vector<float> lnpack;
   std::vector<float> gru_w, gru_bzr, gru_bh;
   std::vector<float> pre_sub, pre_div, pre_mul;
   std::vector<int> skip[GO2PI_MAX_LAYERS];  // each layer's observation column indices (DevProgram::skip_idx)
@@ -95,7 +102,7 @@ struct Plan {
   bool has_ln = false;         // a LayerNormalization on any layer
   bool has_skip = false;       // an observation skip input on any layer (small-batch kernels: Switches::skip_small)
   // a residual connection on any layer (policy_fused_res_kernel<8> and the GEMV chain; small-batch kernels:
-  // Switches::residual_small)
+  // Switches::residual_small; the pipeline's policy_mlp_res_kernel: Switches::residual_batched)
   bool has_res = false;
   go2pi_cost cost{};
   // whether build() sets up the resident path (the request ring and its kernel)

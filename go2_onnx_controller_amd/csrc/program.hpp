@@ -152,6 +152,10 @@ struct DevProgram {
   // activation (a pre-LN layer's DevLayer::act is none), bpack the LN pack and nbias its
   // floats: [3][nl - 1][64 tpw], the hidden biases back to back, then every hidden layer's
   // Scale, then every hidden layer's B (zeros for a layer without LN).
+  // A program with residual connections (res[] below) and w4ln_tpw > 0 is the pipeline's residual
+  // form (GO2PI_RESIDUAL_BATCHED, plan.cpp): batched launches run policy_mlp_res_kernel on the
+  // same fields, with or without an LN; hid_act is then not read (the hidden layers need not
+  // share an activation: the kernel reads each layer's own). No field of its own marks it.
   int w4ln_tpw;
   const float *w4_bpack;  // pipeline: those biases packed back to back in device memory (one LDS-DMA stream)
   int w4_plain;           // pipeline, 1: no prologue / epilogue arithmetic, no recurrent cell (the lean kernel)
@@ -185,7 +189,9 @@ struct DevProgram {
   // Residual connections (onnx_model.hpp Dense::res): res[l] = j + 1 where layer j's carried
   // value is added to layer l's Gemm (+ bias) output in front of its activation / LN, 0: none
   // (so a zeroed program has none). Served by policy_fused_res_kernel and the GEMV chain, and
-  // by policy_latency_res_kernel / policy_resident_kernel<.., RES> (GO2PI_RESIDUAL_SMALL).
+  // by policy_latency_res_kernel / policy_resident_kernel<.., RES> (GO2PI_RESIDUAL_SMALL) and, for
+  // batched launches of a program of the pipeline's shape, by policy_mlp_res_kernel
+  // (GO2PI_RESIDUAL_BATCHED; w4ln_tpw above).
   int res[GO2PI_MAX_LAYERS];
 };
 
@@ -222,7 +228,8 @@ inline bool program_has_skip(const DevProgram &p) {
 
 // a residual connection on any layer: served by the general batched body's residual
 // instantiation (policy_fused_res_kernel<8>) and the GEMV chain, and with GO2PI_RESIDUAL_SMALL
-// by the small-batch kernels' residual instantiations (plan.cpp plan_program)
+// by the small-batch kernels' residual instantiations, with GO2PI_RESIDUAL_BATCHED and w4ln_tpw
+// != 0 by the pipeline's policy_mlp_res_kernel for batched launches (plan.cpp plan_program)
 inline bool program_has_res(const DevProgram &p) {
   for (int l = 0; l < p.nl; ++l)
     if (p.res[l]) return true;

@@ -1,5 +1,7 @@
 // The 4-wave pipeline for dense policies with LayerNormalization: policy_mlp_ln_kernel<TPW, HT>
-// (opts.ln_small bit GO2PI_LN_BATCHED; plan.cpp decides, kernels_w4ln.inc launches).
+// (opts.ln_small bit GO2PI_LN_BATCHED; plan.cpp decides, kernels_w4ln.inc launches), and the
+// same body with residual connections, policy_mlp_res_kernel<TPW, HT> (GO2PI_RESIDUAL_BATCHED,
+// kernels_w4res.inc; the RES parameter of w4ln_body and w4ln_epi, described at w4ln_body).
 //
 // The pipeline is w4_step's (fused_impl.hpp), built from the same parts (w4_prefill,
 // w4_lds_phase, w4_chunk, w4_wait): 4 waves, one 16-robot tile per workgroup, wave w owns
@@ -88,16 +90,36 @@ __device__ __forceinline__ void w4ln_act(float4 (&v)[TPW], const ActP &ap) {
 // layer's B operand). lp: this lane's bias float4 of tile t0 of this layer in the LDS pack,
 // Scale and B `gofs` and 2 * gofs floats behind it; mode: 0 act(x), 1 act(LN(x)), 2 LN(act(x));
 // col0: this lane's first column of tile t0.
-template <int TPW>
+// RES (policy_mlp_res_kernel): the layer's residual connection, on the registers. cons: the
+// layer adds the carried value, (acc + bias) + carried, in front of the activation and the LN
+// (the order of dense_store, tile_finish and the small-batch forms); src: it then keeps what
+// its dense store would write before any LN pass, the raw sum of a pre-LN layer (mode 1: no
+// activation yet) and the activated value of mode 0 and mode 2. A layer that is both reads
+// before it overwrites. carried: the lane's TPW values. Without RES nothing of this is compiled.
+template <int TPW, bool RES = false>
 __device__ __forceinline__ void w4ln_epi(float4 (&v)[TPW], const f32x4 (&acc)[TPW], const float *lp, int gofs, int mode,
                                          float eps, int N, const ActP &ap, int col0, float *rsum, float *rvar,
-                                         int wave, int lane) {
+                                         int wave, int lane, [[maybe_unused]] float4 *carried = nullptr,
+                                         [[maybe_unused]] bool cons = false, [[maybe_unused]] bool src = false) {
 #pragma unroll
   for (int i = 0; i < TPW; ++i) {
     const float4 bv = *reinterpret_cast<const float4 *>(lp + i * 16);
     v[i] = make_float4(acc[i][0] + bv.x, acc[i][1] + bv.y, acc[i][2] + bv.z, acc[i][3] + bv.w);
   }
+  if constexpr (RES) {
+    if (cons) {
+#pragma unroll
+      for (int i = 0; i < TPW; ++i)
+        v[i] = make_float4(v[i].x + carried[i].x, v[i].y + carried[i].y, v[i].z + carried[i].z, v[i].w + carried[i].w);
+    }
+  }
   if (mode != 1) w4ln_act<TPW>(v, ap);
+  if constexpr (RES) {
+    if (src) {
+#pragma unroll
+      for (int i = 0; i < TPW; ++i) carried[i] = v[i];
+    }
+  }
   if (mode == 0) return;
   const float fn = (float)N;
   float s = 0.f;
@@ -132,9 +154,36 @@ __device__ __forceinline__ void w4ln_epi(float4 (&v)[TPW], const f32x4 (&acc)[TP
   if (mode == 1) w4ln_act<TPW>(v, ap);
 }
 
+// The residual kernel's state (w4ln_body, RES): the two layer masks and the lane's carried value.
+template <int TPW, bool RES>
+struct W4ResState {};
+template <int TPW>
+struct W4ResState<TPW, true> {
+  unsigned consm, srcm;
+  float4 carried[TPW];
+};
+
 // dims = in_dim | c0 << 12 | hidden layers << 20 (c0: layer 0's k-chunks, a multiple of 4).
 // pack: DevProgram::bpack of an LN pipeline program (program.hpp w4ln_tpw).
-template <int TPW, int HT>
+//
+// RES (policy_mlp_res_kernel<TPW, HT>, GO2PI_RESIDUAL_BATCHED): residual connections
+// (DevProgram::res). Wave w owns the same tiles of every hidden layer and all hidden layers
+// have one padded width, so a lane holds the same (robot, column) elements in v[] at every
+// hidden layer's epilogue, and a consumer has the width of its source (loader rule): the
+// carried value stays in the lane's registers (carried[TPW]) from the source's epilogue to
+// the consumer's, with no LDS tile, no barrier and no traffic. P.res[] is read once into two
+// scalar masks; carried[] is zero at the start of every step. The hidden layers need not
+// share an activation (SimBa: none / Relu / none), so each layer's is read from P.L[l] (a
+// pre-LN layer's from its ln_act), never from the hot block's hid_act; a layer without LN runs
+// mode 0 against zero Scale / B in the pack. The loader refuses an Add on the output layer:
+// the head is the LN kernel's.
+// Pad columns (>= N) under RES: their weight rows and biases are zero, so such a column holds
+// act(0), or act(0 + carried) where the carried pad is itself such a value: a finite sum of
+// act(0) constants of the layers before, the same in every row. It is excluded from every LN by
+// index (and written 0 behind one), and it meets only zero weight columns in the next layer
+// and the head (a consumer's N is its source's N, and every layer's K is its predecessor's N).
+// The order of every addition still depends on the column, N and the wave alone.
+template <int TPW, int HT, bool RES = false>
 __device__ __forceinline__ void w4ln_body(const DevProgram &P, const float *__restrict__ obs, float *__restrict__ act,
                                           const float *l0w, const float *pack, int B, int steps, unsigned dims,
                                           unsigned *yield) {
@@ -171,6 +220,27 @@ __device__ __forceinline__ void w4ln_body(const DevProgram &P, const float *__re
   for (int i = 0; i < TPW; ++i) vo[i] = ((t0 + i) * 64 + lane) * 16;
   auto layer_w = [&](int l) { return l0w + (size_t)(c0 + (l - 1) * CH) * CH * 256; };  // (w4_layer_w)
   int ep = 0;  // flag epochs published so far (the same in every wave)
+  // (RES) consm bit l: hidden layer l adds the carried value; srcm bit l: its value is one.
+  // Read here, once (as fused_body reads them): the per-layer tests are scalar arithmetic
+  // (and the carried value itself; without RES the struct is empty)
+  [[maybe_unused]] W4ResState<TPW, RES> rs;
+  if constexpr (RES) {
+    unsigned consm = 0, srcm = 0;
+#pragma unroll
+    for (int l = 0; l < GO2PI_MAX_LAYERS; ++l) {
+      const unsigned r = l < nh ? (unsigned)P.res[l] : 0u;  // j + 1, 0: none
+      consm |= (r != 0u ? 1u : 0u) << l;
+      srcm |= r ? 1u << (r - 1) : 0u;
+    }
+    rs.consm = __builtin_amdgcn_readfirstlane(consm);
+    rs.srcm = __builtin_amdgcn_readfirstlane(srcm);
+  }
+  // (RES) the epilogue's activation of hidden layer PL: the layer's own, a pre-LN layer's from its ln_act
+  [[maybe_unused]] auto layer_act = [](const DevLayer &PL, int mode) {
+    const bool pre = mode == 1;
+    return ActP{__builtin_amdgcn_readfirstlane(pre ? PL.ln_act : PL.act), pre ? PL.ln_alpha : PL.alpha,
+                pre ? PL.ln_beta : PL.beta};
+  };
   for (int step = 0; step < steps; ++step) {
     // wave w stages rows w, w + NW, ... in whole 64-column chunks by direct-to-LDS loads;
     // padding lanes read an element of the same row (times a zero weight column), rows past
@@ -196,7 +266,12 @@ __device__ __forceinline__ void w4ln_body(const DevProgram &P, const float *__re
     unsigned *err = P.err_hot;
     const int head_n = P.head_n, head_act = P.head_act;
     const float head_alpha = P.head_alpha, head_beta = P.head_beta;
-    const ActP ap{P.hid_act, P.hid_alpha, P.hid_beta};
+    // (RES: not used, and so not read: every epilogue takes its layer's own, layer_act)
+    [[maybe_unused]] const ActP ap{P.hid_act, P.hid_alpha, P.hid_beta};
+    if constexpr (RES) {
+#pragma unroll
+      for (int i = 0; i < TPW; ++i) rs.carried[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     // layer 0's input rows and the pack are in LDS (this wave's direct-to-LDS loads, older
     // than the ring's RD * TPW loads, which stay in flight)
     wg_barrier_vm<RD * TPW>();
@@ -238,7 +313,11 @@ __device__ __forceinline__ void w4ln_body(const DevProgram &P, const float *__re
       float *yrow = Y + (lane & 15) * S + col0;
       // layer l - 1's epilogue for all the wave's tiles, to registers and to LDS
       float4 v[TPW];
-      w4ln_epi<TPW>(v, acc, lp0 + (l - 1) * W, gofs, mode, eps, N, ap, col0, rsum, rvar, wave, lane);
+      if constexpr (RES)
+        w4ln_epi<TPW, true>(v, acc, lp0 + (l - 1) * W, gofs, mode, eps, N, layer_act(PL, mode), col0, rsum, rvar, wave,
+                            lane, rs.carried, (rs.consm >> (l - 1)) & 1u, (rs.srcm >> (l - 1)) & 1u);
+      else
+        w4ln_epi<TPW>(v, acc, lp0 + (l - 1) * W, gofs, mode, eps, N, ap, col0, rsum, rvar, wave, lane);
 #pragma unroll
       for (int i = 0; i < TPW; ++i) *reinterpret_cast<float4 *>(yrow + i * 16) = v[i];
       if constexpr (HO) {
@@ -279,7 +358,11 @@ __device__ __forceinline__ void w4ln_body(const DevProgram &P, const float *__re
       const int mode = __builtin_amdgcn_readfirstlane(PL.ln), N = __builtin_amdgcn_readfirstlane(PL.N);
       const float eps = PL.ln_eps;
       float4 v[TPW];
-      w4ln_epi<TPW>(v, acc, lp0 + (nh - 1) * W, gofs, mode, eps, N, ap, col0, rsum, rvar, wave, lane);
+      if constexpr (RES)
+        w4ln_epi<TPW, true>(v, acc, lp0 + (nh - 1) * W, gofs, mode, eps, N, layer_act(PL, mode), col0, rsum, rvar, wave,
+                            lane, rs.carried, (rs.consm >> (nh - 1)) & 1u, (rs.srcm >> (nh - 1)) & 1u);
+      else
+        w4ln_epi<TPW>(v, acc, lp0 + (nh - 1) * W, gofs, mode, eps, N, ap, col0, rsum, rvar, wave, lane);
       f32x4 hacc[HT][4];
 #pragma unroll
       for (int h = 0; h < HT; ++h)
@@ -331,6 +414,17 @@ __global__ __launch_bounds__(256) void policy_mlp_ln_kernel(const float *__restr
                                                             const DevProgram *__restrict__ Pd, int B, int steps,
                                                             unsigned dims, unsigned *yield) {
   w4ln_body<TPW, HT>(*Pd, obs, act, l0w, pack, B, steps, dims, yield);
+}
+
+// The same pipeline with residual connections (w4ln_body's RES; GO2PI_RESIDUAL_BATCHED,
+// kernels_w4res.inc launches): a residual program with or without LayerNormalization.
+template <int TPW, int HT>
+__global__ __launch_bounds__(256) void policy_mlp_res_kernel(const float *__restrict__ obs, float *__restrict__ act,
+                                                             const float *__restrict__ l0w,
+                                                             const float *__restrict__ pack,
+                                                             const DevProgram *__restrict__ Pd, int B, int steps,
+                                                             unsigned dims, unsigned *yield) {
+  w4ln_body<TPW, HT, true>(*Pd, obs, act, l0w, pack, B, steps, dims, yield);
 }
 
 }  // namespace go2pi

@@ -70,4 +70,15 @@ int w4ln_launch(const DevProgram &p, const DevProgram *p_dev, const float *obs, 
 template <int TPW>
 int w4ln_name(const DevProgram &p, char *buf, size_t cap);  // w4ln_launch's kernel (batched_kernel_name)
 
+// The pipeline's residual kernel (policy_mlp_res_kernel; a program with w4ln_tpw != 0 and
+// residual connections, GO2PI_RESIDUAL_BATCHED): the layout, the pack and the launch arguments
+// above; one translation unit per tiles per wave (kernels_w4res_t{2,4,8}.hip).
+template <int TPW>
+int w4res_configure(const DevProgram &p);
+template <int TPW>
+int w4res_launch(const DevProgram &p, const DevProgram *p_dev, const float *obs, float *act, int batch, int steps,
+                 void *stream);
+template <int TPW>
+int w4res_name(const DevProgram &p, char *buf, size_t cap);
+
 }  // namespace go2pi

@@ -186,6 +186,8 @@ class Engine:
         # resident_ms > 0, a resident kernel (False: one launch per layer)
         # ln_batched: batched launches of a dense LN policy of the pipeline's shape on
         # policy_mlp_ln_kernel (False: the general batched kernel). go2pi.h GO2PI_LN_SMALL | GO2PI_LN_BATCHED
+        # (a policy with residual connections: GO2PI_RESIDUAL_BATCHED in the environment, read by the library when
+        # the engine is created, puts its batched launches on policy_mlp_res_kernel; ln_batched has no effect on it)
         o.ln_small = int(bool(ln_small)) | 2 * int(bool(ln_batched))
         h = ctypes.c_void_p()
         if isinstance(model, (bytes, bytearray)):

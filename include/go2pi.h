@@ -135,7 +135,20 @@ void go2pi_default_opts(go2pi_opts *opts);
    small_batch by policy_latency_kernel and, with resident_ms > 0, by the multi-workgroup
    policy_resident_kernel (never by a single-workgroup or the wide resident kernel); a
    policy that also has a LayerNormalization (every SimBa model) needs ln_small's bit 1 as
-   well, one that also has a skip input GO2PI_SKIP_SMALL. go2pi_inspect_model reports each layer's
+   well, one that also has a skip input GO2PI_SKIP_SMALL. With GO2PI_RESIDUAL_BATCHED set in
+   the environment when the engine is created (to any value; it holds for the engine's life;
+   an environment switch because go2pi_opts ends in ln_small) the batched launches of a
+   residual policy of the 4-wave pipeline's shape run on policy_mlp_res_kernel<tiles per wave,
+   head tiles>, which keeps the carried value in registers: no skip input, opts.waves = 0,
+   every hidden layer's width padded to 64 the same 128, 256 or 512 (the activations may
+   differ from layer to layer), an output layer of at most 32 columns (16 at 512), an
+   observation no wider than the hidden layers, and no prologue (obs_mean / obs_std / clip,
+   Sub / Div / Mul / Clip nodes) or action post-processing. It needs no LayerNormalization
+   and no ln_small bit. Any other residual policy, and opts.waves = 8, keep
+   policy_fused_res_kernel<8>; waves = 4 / 16 stay refused, batches <= small_batch, the
+   resident kernel and go2pi_controller_step* are what they are without the switch, and the
+   switch has no effect on a policy without residual connections. go2pi_batched_kernel
+   names the kernel. go2pi_inspect_model reports each layer's
    "res": the index of the layer whose carried value it adds, or -1.
    LayerNormalization (opset 17, over the feature axis, epsilon from the attribute, Scale
    and optional B constant, only output 0 used) is accepted on any dense layer but the last,
