@@ -1408,6 +1408,18 @@ int go2pi_controller_step_device(go2pi_engine *e, const float *state, const floa
     check_ctl(e, batch);
     if (batch == 0) return GO2PI_OK;
     if (!state || !obs || !action) throw ApiError("null state/obs/action buffer", GO2PI_E_INVALID);
+    // the buffer contract (go2pi.h): the batched tick's head lane writes its four joints of
+    // action, q_des, kp and kd with 16-byte stores (ctl_fn.hpp ctl_store4), straight to these
+    // pointers; refused here, before anything is enqueued
+    auto aligned16 = [](const void *p, const char *name) {
+      if (reinterpret_cast<uintptr_t>(p) & 15)
+        throw ApiError(std::string("go2pi_controller_step_device: ") + name + " must be 16-byte aligned",
+                       GO2PI_E_INVALID);
+    };
+    aligned16(action, "action_dev");
+    aligned16(q_des, "q_des_dev");
+    aligned16(kp, "kp_dev");
+    aligned16(kd, "kd_dev");
     hip_check(hipSetDevice(e->device), "hipSetDevice");
     // a live resident kernel shares the granules, epoch and error words the batch <= 8
     // launch uses: it leaves first (as for every other call on the engine)

@@ -184,6 +184,36 @@ int go2pi_io_shape(const go2pi_engine *e, int32_t is_output, int32_t index, int6
 /* Per-robot feature counts of the bound observation / action (shape[1]). */
 int go2pi_io_dims(const go2pi_engine *e, int64_t *in_dim, int64_t *out_dim);
 
+/* ---------------------------------------------------------------------------
+   Buffer contract (every entry point that takes rows; tests/test_gpu_abi_confinement.py).
+   Rows [0, batch) only: a call reads and writes rows [0, batch) of the buffers it is given
+   and no byte outside them, so a buffer may be a sub-range of a larger allocation of the
+   caller's with live data on either side. Nothing a call returns depends on what lies
+   outside those rows (the kernels work in 16-row tiles; in the last tile the rows past
+   `batch` are computed from zeros or from a copy of row batch - 1, never from the caller's
+   memory, and are never stored).
+   Inputs are never written: obs / obs_dev of the run paths, state and joy of the
+   controller tick. (The tick's obs and action are in/out by design, see below.)
+   The engine's own recurrent state obeys the same rule: a call on `batch` robots advances
+   hidden rows [0, batch) and leaves rows [batch, max_batch) bit-identical;
+   go2pi_reset_hidden(mask, batch) zeroes exactly the masked rows below `batch`.
+   Alignment, per entry point:
+     go2pi_run, go2pi_controller_step (host pointers)     the natural alignment of the element
+         type (4 bytes for float / uint32_t, 8 for double): the rows are staged through
+         engine-owned, 256-byte-aligned buffers and copied to and from the caller's.
+     go2pi_run_device, go2pi_run_sequence_device          obs_dev and act_dev 4 bytes. (When
+         act_dev is 16-byte aligned and out_dim is a multiple of 4 the batched kernels store
+         four actions at a time, else one: the same values either way, bit for bit.)
+     go2pi_controller_step_device                         action_dev, q_des_dev, kp_dev and
+         kd_dev 16 bytes each (a NULL optional output is exempt): the batched tick writes a
+         robot's joints four at a time with 16-byte stores (one float4, or two doubles) at
+         byte offsets that are multiples of 16 from the pointer (a row is 48 or 96 bytes).
+         state_dev, joy_dev, obs_dev and status_dev 4 bytes: they are read through 4-byte
+         direct-to-LDS loads and written one element at a time. A pointer that breaks this
+         is refused with GO2PI_E_INVALID and a message that names it, before anything is
+         enqueued; no buffer is touched. A row range [r0, r1) of 16-byte-aligned [B][12]
+         arrays is itself aligned, so sharding a fleet by rows needs no care. */
+
 /* Synchronous host path: obs [batch][in_dim] -> act [batch][out_dim], host memory
    (the act() contract: reads obs at call time, overwrites act in place). */
 int go2pi_run(go2pi_engine *e, const float *obs, float *act, int64_t batch);
@@ -191,13 +221,15 @@ int go2pi_run(go2pi_engine *e, const float *obs, float *act, int64_t batch);
 /* Asynchronous device path: obs/act are device pointers on e's device; enqueued on
    `hip_stream` (a hipStream_t; NULL = the HIP null stream, as in HIP). No host sync.
    The caller must use the same HIP runtime instance as this library (e.g. load
-   PyTorch's libamdhip64 first when sharing torch streams/tensors). */
+   PyTorch's libamdhip64 first when sharing torch streams/tensors).
+   Buffers: rows [0, batch) only, obs_dev never written, 4-byte alignment (above). */
 int go2pi_run_device(go2pi_engine *e, const float *obs_dev, float *act_dev, int64_t batch, void *hip_stream);
 
 /* Recurrent policies carry one hidden row per robot (engine-resident, HBM).
    Run `steps` ticks back to back with the hidden rows kept on-chip between ticks:
    obs_dev [steps][batch][in_dim] -> act_dev [steps][batch][out_dim]. For a
-   feed-forward policy this is `steps` independent batched calls. */
+   feed-forward policy this is `steps` independent batched calls.
+   Buffers: exactly steps * batch rows of each, obs_dev never written, 4-byte alignment. */
 int go2pi_run_sequence_device(go2pi_engine *e, const float *obs_dev, float *act_dev, int64_t steps,
                               int64_t batch, void *hip_stream);
 
@@ -313,7 +345,10 @@ int go2pi_ctl_history(const go2pi_engine *e, int32_t *history);
    one launch on host-mapped staging, larger batches stage through HBM). */
 int go2pi_controller_step(go2pi_engine *e, const float *state, const float *joy, float *obs, float *action,
                           double *q_des, double *kp, double *kd, uint32_t *status, int64_t batch);
-/* Same on device pointers, enqueued on `hip_stream`, no host sync. */
+/* Same on device pointers, enqueued on `hip_stream`, no host sync. Buffers (the buffer
+   contract above): rows [0, batch) only; state_dev and joy_dev never written; action_dev
+   and the q_des_dev / kp_dev / kd_dev that are passed must be 16-byte aligned, else
+   GO2PI_E_INVALID and nothing is enqueued. */
 int go2pi_controller_step_device(go2pi_engine *e, const float *state_dev, const float *joy_dev, float *obs_dev,
                                  float *action_dev, double *q_des_dev, double *kp_dev, double *kd_dev,
                                  uint32_t *status_dev, int64_t batch, void *hip_stream);

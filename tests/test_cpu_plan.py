@@ -20,6 +20,7 @@ import pytest
 import graphs
 import ln_small_models as lm
 import probe_models as pm
+import test_gpu_abi_confinement as abi
 import test_gpu_lean_tick as lean_tick
 import test_gpu_lean_transition as lean_transition
 import test_gpu_probe_activations as probe_act
@@ -122,6 +123,28 @@ def test_ln_small_selection(tmp_path, name):
     assert plan(p, use_graph=False)["small_kernel"] == "gemv_layer_kernel"
     got = plan(p, small_batch=-1, ln_small=True)
     assert got["small_kernel"] == got["batched_kernel"]
+
+
+@pytest.mark.parametrize("row", abi.TABLE + [r for r in abi.ALIGN_ROWS if r not in abi.TABLE], ids=lambda r: r.id)
+def test_abi_confinement_table(tmp_path, row):
+    """tests/test_gpu_abi_confinement.py's table: the batched kernel every row names (a prefix)
+    and what serves its batches <= 8."""
+    src = abi._source(row.model)
+    p = _write(tmp_path, row.id, src) if isinstance(src, bytes) else src
+    opts = dict(row.opts)
+    if opts.pop("ln_batched", False):
+        opts["ln_small"] = 2  # go2pi.h GO2PI_LN_BATCHED
+    got = plan(p, *[f"{k}={v}" for k, v in row.env.items()], **opts)
+    assert got["batched_kernel"].startswith(row.kernel)
+    assert got["small_kernel"] == (row.small or got["batched_kernel"])
+
+
+def test_abi_confinement_table_reaches_every_batched_body():
+    """Every name kernels.hip batched_kernel_name can give has a row: the general body at 4, 8
+    and 16 waves, the pipeline's general body, the lean kernel in both forms, the lean
+    recurrent ticks, the LN and the residual pipeline, the general residual kernel."""
+    for fam in abi.FAMILIES:
+        assert any(r.kernel.startswith(fam) for r in abi.TABLE), fam
 
 
 # ---- 2. the switches (plan.hpp Switches)
